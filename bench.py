@@ -12,7 +12,13 @@ per-iteration f64 per-edge records are exchanged with an RCCL all-gather inside 
 rank then assembles all edges in edge order: DESIGN.md §6) -> strong scaling; value = total
 pair-iterations / max-over-ranks wall time.
 
-Extra fields: ``roofline`` for the dominant kernel (the per-iteration accumulate kernel,
+A plain run sets up, warms up, times the steps and prints the headline line (``metric``,
+``value``, ``ms_per_step``, ... and the workload's ``config``); ``--dump-outputs DIR`` also writes
+what the last timed call returned to its caller (the poses it updated in place and its last step)
+as ``DIR/Twc.npy`` and ``DIR/dx.npy``.  Everything below takes runs of its own and is measured
+only with ``--full`` (where ``--no-cpu-baseline``, ``--no-matching`` and ``--no-cfg4`` trim it).
+
+Extra fields (``--full``): ``roofline`` for the dominant kernel (the per-iteration accumulate kernel,
 HBM-bound, timed with HIP events on its stream during the timed steps).  Its algorithmic bytes
 are those of the packed formulation it runs: per directed point-edge the 8-B
 iteration-invariant record {match | invalid bit, sqrt q} + Xj 12 B + the matched point (calib:
@@ -54,10 +60,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg3", choices=["cfg1", "cfg2", "cfg3", "cfg4"])
     ap.add_argument("--iters", type=int, default=None, help="GN iterations per op call")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-matching", action="store_true", help="skip the matching-kernel section")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: phase times and roofline, CPU baseline and accuracy, "
+                         "the configs[3] block, the matching and tracking sections")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed call's outputs (Twc, dx) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and accuracy")
+    ap.add_argument("--no-matching", action="store_true", help="with --full: skip the matching-kernel section")
     ap.add_argument("--no-cfg4", action="store_true",
-                    help="skip the configs[3] block (1024-edge graph, edge-sharded like the headline config)")
+                    help="with --full: skip the configs[3] block (1024-edge graph, edge-sharded like the "
+                         "headline config)")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "accum_traffic.json"))
     return ap.parse_args()
 
@@ -101,11 +113,12 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world} (launch one rank per GPU)")
+    also_cfg4 = args.full and args.config != "cfg4" and not args.no_cfg4
     if os.environ.get("M3S_BENCH_SPAWN_CHECK"):  # tests/test_bench_cli.py: the launch, no GPU work
         from m3s import synth
         from m3s.dist import shard_range
         plan = {c: list(shard_range(2 * synth.CONFIGS[c]["E"], world, rank))
-                for c in ([args.config] + (["cfg4"] if args.config != "cfg4" and not args.no_cfg4 else []))}
+                for c in ([args.config] + (["cfg4"] if also_cfg4 else []))}
         print(json.dumps({"rank": rank, "world": world, "local_rank": local_rank, "edge_ranges": plan}),
               flush=True)
         return
@@ -127,40 +140,18 @@ def main():
     from m3s.dist import HostComm, RcclComm
 
     comm = (HostComm() if rehearse else RcclComm(rank, world, device=dev)) if world > 1 else None
-    r = time_config(args.config, args.iters, args.steps, args.warmup, world, rank, rehearse, dev, comm)
-    g, mode, iters, E_und, lo, hi = r["g"], r["mode"], r["iters"], r["E_und"], r["lo"], r["hi"]
+    r = time_config(args.config, args.iters, args.steps, args.warmup, world, rank, rehearse, dev, comm,
+                    full=args.full, keep_outputs=args.dump_outputs is not None)
+    g, mode, iters, E_und = r["g"], r["mode"], r["iters"], r["E_und"]
     Twc0, Twc, elapsed = r["Twc0"], r["Twc"], r["elapsed"]
-    prof, nprof, ph, nph, ray_path = r["prof"], r["nprof"], r["ph"], r["nph"], r["ray_path"]
-    acc_events = r["acc_events"]
-    n_ph = max(nph.value, 1)
     from m3s import synth
 
     spec = synth.CONFIGS[args.config]
     E_dir = 2 * E_und
     pair_iters = E_und * iters * args.steps
     value = pair_iters / elapsed
-    n_it = max(nprof.value, 1)
-    acc_ms = prof[0] / n_it if acc_events else ph[0] / n_ph
-    # a calib call's first accumulate builds the packed records itself (M3S_GN_PACK_FIRST):
-    # another kernel, timed apart from the iteration kernel the roofline prices
-    first_ms = prof[1] / prof[2] if acc_events and prof[2] > 0 else None
-    packed = iters >= 3 and os.environ.get("M3S_GN_PACK", "1") != "0"
-    bpe = (RAY_BYTES_PER_POINT_EDGE if ray_path else PACKED_BYTES_PER_POINT_EDGE[mode]) if packed \
-        else REF_BYTES_PER_POINT_EDGE
-    stream = ("packed, ray-constrained Xj (depth only)" if ray_path else "packed") if packed \
-        else "reference tensors"
-    bytes_launch = bpe * g.HW * (hi - lo)
-    ref_bytes_launch = REF_BYTES_PER_POINT_EDGE * g.HW * (hi - lo)
-    achieved = bytes_launch / (acc_ms * 1e-3) / 1e9 if acc_ms > 0 else None
-    traffic = None
-    if os.path.exists(args.traffic_file):
-        try:
-            tf = json.load(open(args.traffic_file))
-            if (tf.get("config") == args.config and tf.get("n_gpus", 1) == world
-                    and tf.get("packed", False) == packed and tf.get("stream") == stream):
-                traffic = tf.get("hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, r["outputs"])
 
     out = {
         "metric": METRIC,
@@ -189,6 +180,79 @@ def main():
                                                          if rehearse else " + RCCL all-gather of the per-edge records")
                                                         if world > 1 else ""),
         },
+    }
+    if args.full:
+        out.update(headline_detail(args, r, world))
+        out["cpu_baseline"] = None
+
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(g, mode, E_und, iters)
+        out["accuracy"] = accuracy(g, mode, Twc0, Twc, cpu_baseline.last_poses,
+                                   cpu_baseline.exact_poses, cpu_baseline.full_poses, iters,
+                                   cpu_baseline.last_step, cpu_baseline.exact_step)
+        out["accuracy"]["timed_kernel_parity"] = timed_kernel_parity(g, mode, Twc0, cpu_baseline.refs)
+        if os.environ.get("M3S_BENCH_REF_ORDER", "1") != "0":
+            out["accuracy"]["reference_order_mode"] = reference_order_block(g, mode, Twc0, args, iters)
+        if mode == "calib" and os.environ.get("M3S_BENCH_STRESS", "1") != "0":
+            out["accuracy"]["stress_1iter"] = stress_block(dev)
+    # BASELINE.json configs[3] (1024 edges, the config SURVEY §8(e) sets the scaling target on):
+    # with --gpus N it is edge-sharded like the headline config, so the driver's SCALE run
+    # measures it at every N.  Its own block; ``value`` stays the headline config's.
+    if also_cfg4:
+        del g, Twc0, Twc, r  # the headline graph is not needed any more
+        torch.cuda.empty_cache()
+        out["cfg4"] = config_block("cfg4", args, world, rank, rehearse, dev, comm)
+    if args.full and rank == 0 and world == 1 and not args.no_matching:
+        out["matching"] = matching_bench(dev)
+        out["tracking"] = tracking_bench(dev)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if comm is not None:
+        comm.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, outputs):
+    """``--dump-outputs``: what the last timed call gave its caller, one float32 ``.npy`` each."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32, copy=False))
+
+
+def headline_detail(args, r, world):
+    """``--full``: the headline config's phase times, solve path and accumulate roofline (from the
+    events of the timed steps and the two extra untimed steps of ``time_config``)."""
+    g, mode, iters, lo, hi = r["g"], r["mode"], r["iters"], r["lo"], r["hi"]
+    prof, nprof, ph, nph, ray_path = r["prof"], r["nprof"], r["ph"], r["nph"], r["ray_path"]
+    acc_events = r["acc_events"]
+    n_ph = max(nph.value, 1)
+    n_it = max(nprof.value, 1)
+    acc_ms = prof[0] / n_it if acc_events else ph[0] / n_ph
+    # a calib call's first accumulate builds the packed records itself (M3S_GN_PACK_FIRST):
+    # another kernel, timed apart from the iteration kernel the roofline prices
+    first_ms = prof[1] / prof[2] if acc_events and prof[2] > 0 else None
+    packed = iters >= 3 and os.environ.get("M3S_GN_PACK", "1") != "0"
+    bpe = (RAY_BYTES_PER_POINT_EDGE if ray_path else PACKED_BYTES_PER_POINT_EDGE[mode]) if packed \
+        else REF_BYTES_PER_POINT_EDGE
+    stream = ("packed, ray-constrained Xj (depth only)" if ray_path else "packed") if packed \
+        else "reference tensors"
+    bytes_launch = bpe * g.HW * (hi - lo)
+    ref_bytes_launch = REF_BYTES_PER_POINT_EDGE * g.HW * (hi - lo)
+    achieved = bytes_launch / (acc_ms * 1e-3) / 1e9 if acc_ms > 0 else None
+    traffic = None
+    if os.path.exists(args.traffic_file):
+        try:
+            tf = json.load(open(args.traffic_file))
+            if (tf.get("config") == args.config and tf.get("n_gpus", 1) == world
+                    and tf.get("packed", False) == packed and tf.get("stream") == stream):
+                traffic = tf.get("hbm_bytes_per_launch")
+        except Exception:
+            traffic = None
+
+    return {
         "phase_ms_per_iter": {
             "accumulate": acc_ms,
             "reduce_compact_allreduce": ph[1] / n_ph,
@@ -214,42 +278,16 @@ def main():
             "launch_ms_spread": launch_spread(r["launch_ms"]),
             "first_accumulate_with_pack_ms": first_ms,
         },
-        "cpu_baseline": None,
     }
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(g, mode, E_und, iters)
-        out["accuracy"] = accuracy(g, mode, Twc0, Twc, cpu_baseline.last_poses,
-                                   cpu_baseline.exact_poses, cpu_baseline.full_poses, iters,
-                                   cpu_baseline.last_step, cpu_baseline.exact_step)
-        out["accuracy"]["timed_kernel_parity"] = timed_kernel_parity(g, mode, Twc0, cpu_baseline.refs)
-        if os.environ.get("M3S_BENCH_REF_ORDER", "1") != "0":
-            out["accuracy"]["reference_order_mode"] = reference_order_block(g, mode, Twc0, args, iters)
-        if mode == "calib" and os.environ.get("M3S_BENCH_STRESS", "1") != "0":
-            out["accuracy"]["stress_1iter"] = stress_block(dev)
-    # BASELINE.json configs[3] (1024 edges, the config SURVEY §8(e) sets the scaling target on):
-    # with --gpus N it is edge-sharded like the headline config, so the driver's SCALE run
-    # measures it at every N.  Its own block; ``value`` stays the headline config's.
-    if args.config != "cfg4" and not args.no_cfg4:
-        del g, Twc0, Twc, r  # the headline graph is not needed any more
-        torch.cuda.empty_cache()
-        out["cfg4"] = config_block("cfg4", args, world, rank, rehearse, dev, comm)
-    if rank == 0 and world == 1 and not args.no_matching:
-        out["matching"] = matching_bench(dev)
-        out["tracking"] = tracking_bench(dev)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if comm is not None:
-        comm.close()
-    if world > 1:
-        dist.destroy_process_group()
 
-
-def time_config(cfg, iters_arg, steps, warmup, world, rank, rehearse, dev, comm):
+def time_config(cfg, iters_arg, steps, warmup, world, rank, rehearse, dev, comm, full=True,
+                keep_outputs=False):
     """Build ``cfg``'s graph (this rank's directed-edge range only), run ``warmup`` untimed op
     calls, then time ``steps`` calls bracketed by a barrier + synchronize on both sides
-    (max over ranks); one more untimed call gives the phase times, another the accumulate path
-    the op took."""
+    (max over ranks).  ``keep_outputs``: copies of what the last timed call returned and updated
+    in place.  ``full``: one more untimed call gives the phase times, another the accumulate
+    path the op took."""
     import mast3r_slam_backends as mb
     from m3s import synth
     from m3s.dist import gauss_newton_sharded, shard_range
@@ -271,15 +309,13 @@ def time_config(cfg, iters_arg, steps, warmup, world, rank, rehearse, dev, comm)
         Twc.copy_(Twc0)
         if world == 1:
             if mode == "calib":
-                mb.gauss_newton_calib(Twc, g.Xs, g.Cs, g.K, g.ii, g.jj, g.idx, g.valid, g.Q, g.H, g.W,
-                                      L["pixel_border"], L["depth_eps"], L["sigma_pixel"],
-                                      L["sigma_depth"], L["C_conf"], L["Q_conf"], iters, 0.0)
-            else:
-                mb.gauss_newton_rays(Twc, g.Xs, g.Cs, g.ii, g.jj, g.idx, g.valid, g.Q, L["sigma_ray"],
-                                     L["sigma_dist"], L["C_conf"], L["Q_conf"], iters, 0.0)
-        else:
-            gauss_newton_sharded(mode, Twc, g.Xs, g.Cs, g.ii, g.jj, g.idx, g.valid, g.Q, lo, comm,
-                                 iters, 0.0, **L)
+                return mb.gauss_newton_calib(Twc, g.Xs, g.Cs, g.K, g.ii, g.jj, g.idx, g.valid, g.Q, g.H, g.W,
+                                             L["pixel_border"], L["depth_eps"], L["sigma_pixel"],
+                                             L["sigma_depth"], L["C_conf"], L["Q_conf"], iters, 0.0)
+            return mb.gauss_newton_rays(Twc, g.Xs, g.Cs, g.ii, g.jj, g.idx, g.valid, g.Q, L["sigma_ray"],
+                                        L["sigma_dist"], L["C_conf"], L["Q_conf"], iters, 0.0)
+        return gauss_newton_sharded(mode, Twc, g.Xs, g.Cs, g.ii, g.jj, g.idx, g.valid, g.Q, lo, comm,
+                                    iters, 0.0, **L)
 
     for _ in range(warmup):
         step()
@@ -294,12 +330,17 @@ def time_config(cfg, iters_arg, steps, warmup, world, rank, rehearse, dev, comm)
         mb.lib.m3s_prof_begin_accum()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        ret = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    # the op's outputs as its caller has them after the last timed call: the poses (updated in
+    # place) and the returned last step, None only with --iters 0 (the untimed calls of --full
+    # write into Twc again)
+    outputs = {k: t.clone() for k, t in (("Twc", Twc), ("dx", ret[0])) if t is not None} \
+        if keep_outputs else None
     prof = (ctypes.c_double * 4)()
     nprof = ctypes.c_int(0)
     mb.lib.m3s_prof_end(prof, ctypes.byref(nprof))
@@ -308,6 +349,16 @@ def time_config(cfg, iters_arg, steps, warmup, world, rank, rehearse, dev, comm)
         buf = (ctypes.c_double * 4096)()
         n_l = mb.lib.m3s_prof_launch_ms(buf, 4096)
         launch_ms = [buf[k] for k in range(min(n_l, 4096))]
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    res = dict(g=g, mode=mode, iters=iters, E_und=E_und, lo=lo, hi=hi, Twc0=Twc0, Twc=Twc,
+               elapsed=elapsed, prof=prof, nprof=nprof, acc_events=acc_events, step=step,
+               launch_ms=launch_ms, outputs=outputs)
+    if not full:
+        mb.gn_check()  # a timed-out factorisation is reported by the next call or here (deferred)
+        return res
     mb.lib.m3s_prof_begin()
     step()
     torch.cuda.synchronize()
@@ -325,14 +376,8 @@ def time_config(cfg, iters_arg, steps, warmup, world, rank, rehearse, dev, comm)
     dbg = (ctypes.c_int * 4)()
     mb.lib.m3s_gn_debug_flags(dbg)
     solve_stats = mb.gn_debug_flags()  # (that call's lagged-factor PCG solves)
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    return dict(g=g, mode=mode, iters=iters, E_und=E_und, lo=lo, hi=hi, Twc0=Twc0, Twc=Twc,
-                elapsed=elapsed, prof=prof, nprof=nprof, ph=ph, nph=nph, ray_path=bool(dbg[3]),
-                acc_events=acc_events, step=step, launch_ms=launch_ms, solve_stats=solve_stats,
-                solve_ms=solve_ms)
+    res.update(ph=ph, nph=nph, ray_path=bool(dbg[3]), solve_stats=solve_stats, solve_ms=solve_ms)
+    return res
 
 
 def _solve_path(st, iters, solve_ms):

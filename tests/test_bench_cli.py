@@ -19,13 +19,13 @@ def _run(args, extra_env):
 
 
 def test_gpus_flag_spawns_one_rank_per_gpu():
-    r = _run(["--gpus", "2"], {"M3S_BENCH_SPAWN_CHECK": "1"})
+    r = _run(["--gpus", "2", "--full"], {"M3S_BENCH_SPAWN_CHECK": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
     assert sorted(d["rank"] for d in lines) == [0, 1]
     assert all(d["world"] == 2 for d in lines)
     assert sorted(d["local_rank"] for d in lines) == [0, 1]
-    # every rank also times BASELINE configs[3] (the 1024-edge cfg4 graph: 2048 directed edges),
+    # with --full every rank also times BASELINE configs[3] (the 1024-edge cfg4 graph: 2048 directed edges),
     # edge-sharded like the headline config: the ranks' ranges tile [0, 2048)
     for cfg, n in (("cfg3", 512), ("cfg4", 2048)):
         ranges = sorted(tuple(d["edge_ranges"][cfg]) for d in lines)
@@ -34,10 +34,32 @@ def test_gpus_flag_spawns_one_rank_per_gpu():
 
 
 def test_cfg4_block_can_be_skipped():
-    r = _run(["--gpus", "1", "--no-cfg4"], {"M3S_BENCH_SPAWN_CHECK": "1"})
+    r = _run(["--gpus", "1", "--full", "--no-cfg4"], {"M3S_BENCH_SPAWN_CHECK": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     (d,) = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
     assert list(d["edge_ranges"]) == ["cfg3"]
+
+
+def test_plain_run_times_the_headline_config_only():
+    r = _run(["--gpus", "1"], {"M3S_BENCH_SPAWN_CHECK": "1"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    (d,) = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert list(d["edge_ranges"]) == ["cfg3"]
+
+
+def test_dump_outputs_writes_one_float32_npy_per_output(tmp_path):
+    import numpy as np
+    import torch
+
+    import bench
+
+    outs = {"Twc": torch.arange(16, dtype=torch.float32).reshape(2, 8), "dx": torch.ones(1, 7)}
+    d = tmp_path / "new" / "dir"
+    bench.dump_outputs(str(d), outs)
+    assert sorted(os.listdir(d)) == ["Twc.npy", "dx.npy"]
+    for name, t in outs.items():
+        a = np.load(d / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, t.numpy())
 
 
 def test_world_size_must_match_gpus_flag():

@@ -1,13 +1,14 @@
 #!/bin/bash
 # A/B of the GN solve variants on the bench graph (cfg3 unless CFG is set): phase ms/iter.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT="${M3S_OUT:-out}"
+mkdir -p $OUT
 CFG="${CFG:-cfg3}"
 run() {  # $1 label, rest env assignments
     local label=$1; shift
-    env "$@" timeout -k 10 120 python bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-matching \
-        > gpurun_out/ab_$label.json 2> gpurun_out/ab_$label.err || { echo "$label FAILED rc=$?"; tail -5 gpurun_out/ab_$label.err; exit 1; }
-    python -c "import json,sys; d=json.load(open('gpurun_out/ab_$label.json')); p=d['phase_ms_per_iter']; print('%-24s ms/step %.3f  acc %.3f sys %.3f solve %.3f retr %.3f' % ('$label', d['ms_per_step'], p['accumulate'], p['reduce_compact_allreduce'], p['solve'], p['retract']))"
+    env "$@" timeout -k 10 120 python bench.py --full --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-matching \
+        > $OUT/ab_$label.json 2> $OUT/ab_$label.err || { echo "$label FAILED rc=$?"; tail -5 $OUT/ab_$label.err; exit 1; }
+    python -c "import json,sys; d=json.load(open('$OUT/ab_$label.json')); p=d['phase_ms_per_iter']; print('%-24s ms/step %.3f  acc %.3f sys %.3f solve %.3f retr %.3f' % ('$label', d['ms_per_step'], p['accumulate'], p['reduce_compact_allreduce'], p['solve'], p['retract']))"
 }
 for v in ${VARIANTS:-default}; do
     case $v in

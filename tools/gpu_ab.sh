@@ -17,7 +17,7 @@ fi
 for cfg in ${CFGS:-cfg3}; do
     for v in ${VARIANTS:-}; do
         env ${ENVS:-} M3S_BACKEND_LIB=$PWD/mast3r-slam_amd/lib/variants/$v.so timeout -k 10 300 \
-            python bench.py --config $cfg ${BENCH_FLAGS:---no-cpu-baseline} --no-matching --steps ${STEPS:-5} --warmup 2 \
+            python bench.py --full --config $cfg ${BENCH_FLAGS:---no-cpu-baseline} --no-matching --steps ${STEPS:-5} --warmup 2 \
             > gpurun_out/ab/${TAG}_${cfg}_$v.json 2> gpurun_out/ab/${TAG}_${cfg}_$v.err
         rc=$?
         if [ $rc -ne 0 ]; then echo "variant $v $cfg rc=$rc"; tail -5 gpurun_out/ab/${TAG}_${cfg}_$v.err; exit $rc; fi

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/pmc_icache
 mkdir -p $OUT
 timeout -s KILL 120 rocprofv3 --pmc SQC_ICACHE_MISSES SQC_ICACHE_HITS SQ_IFETCH --output-format csv -d $OUT -o run -- \
-    python bench.py --steps 1 --warmup 0 --iters 3 --no-cpu-baseline --no-matching > $OUT.log 2>&1
+    python bench.py --full --steps 1 --warmup 0 --iters 3 --no-cpu-baseline --no-matching > $OUT.log 2>&1
 rc=$?; echo "pmc icache rc=$rc"; tail -n 3 $OUT.log
 python tools/pmc_filter.py $OUT
 python - <<'PY'
