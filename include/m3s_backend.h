@@ -129,6 +129,11 @@ void m3s_gn_debug_flags(int* out4);
  * PCG solves that fell back to the direct factorisation, 1 if the call planned PCG iterations,
  * the first PCG iteration (0 if none planned)}. */
 void m3s_gn_pcg_stats(int* out5);
+/* The same call's PCG plan (host plan fields, no synchronisation of their own): out5 = {rows of M
+ * per workgroup (12 or 24), workgroups, 1 if B = M A is staged for one exchange per CG step
+ * (M3S_PCG_ONEX), the lag of M behind the first PCG iteration, the LDS item capacity of a
+ * workgroup's rows of A}; all 0 when the call planned no PCG. */
+void m3s_gn_pcg_plan(int* out5);
 
 /* Deferred error report.  A GN call whose solver has bounded device-side waits (the dataflow
  * factorisation) exports its timeout flag without a host wait.  A call whose wait timed out

@@ -81,6 +81,7 @@ std::vector<double> g_prof_solve_ms;   // the last phase session: each iteration
 
 int g_dbg_flags[4] = {0, 0, 0, 0};  // done, fail, packed, ray-constrained accumulate (last call)
 int g_dbg_pcg[5] = {0, 0, 0, 0, 0};  // PCG solves, their CG steps, fallbacks, PCG planned, first PCG iteration (last call)
+int g_dbg_pcg_plan[5] = {0, 0, 0, 0, 0};  // that call's pcg_R, pcg_nwg, pcg_onex, pcg_lag, pcg_nitem (0 when none planned)
 
 void set_error(const char* fmt, ...) {
     char buf[1024];
@@ -1324,9 +1325,10 @@ int enqueue_solve(const m3s_gn_args& a, Ctx& c, bool fallback = false) {
     // 0.43 ms cooperative groups -- in-kernel a round's chain is ~4 us, but coherent (MALL)
     // block traffic + write-through + the barrier cost as much as the ~5 us launch overhead saved
     static const int coop_mode = env_int("M3S_SOLVE_COOP", 0);
-    // M3S_PCG_FALLBACK_COOP (default 1): a PCG iteration's fallback runs its rounds (and the
-    // hybrid core's fill) as the one all-rounds launch -- slower when it runs, but a converged
-    // PCG skips one launch instead of one per round (cfg3: 5 round launches + the fill)
+    // M3S_PCG_FALLBACK_COOP (default 0; M3S_SOLVE_DF's ticketed launch below took its place) = 1:
+    // a PCG iteration's fallback runs its rounds (and the hybrid core's fill) as the one
+    // all-rounds launch -- slower when it runs, but a converged PCG skips one launch instead of
+    // one per round (cfg3: 5 round launches + the fill)
     static const bool fb_coop = env_int("M3S_PCG_FALLBACK_COOP", 0) != 0;
     // M3S_SOLVE_DF: 1 (default) = a PCG iteration's fallback runs its rounds (and the hybrid core's
     // fill) as ONE plain launch of ticketed targets (sp_rounds_df_kernel: no co-residency); 2 =
@@ -1474,8 +1476,8 @@ void choose_pcg(const m3s_gn_args& a, const Ctx& c, const Plan& plan, int npose,
     const int maxdeg = npose > 0 ? *std::max_element(deg.begin(), deg.end()) : 1;
     auto items = [&](int R) { return 7 * maxdeg * (R / 7 + 2); };
     // (R = threads / 64 or threads / 32: a row's threads stay within one wave, a power of two)
-    // M3S_PCG_ONEX (default 1): one exchange per CG step (B = M A's rows in LDS beside M's) where
-    // they fit (cfg3's 896 unknowns: yes; cfg4's 1792: no -- two exchanges per step)
+    // M3S_PCG_ONEX (default 0: two exchanges per CG step) = 1: one exchange per step (B = M A's
+    // rows in LDS beside M's) where they fit (cfg3's 889 unknowns: yes; cfg4's 1785: no)
     auto pick = [&](bool ox) {
         int R = kPcgThreads / 64;
         auto fits = [&](int r) { return pcg_lds_bytes(n, r, items(r), ox) <= (size_t)kPcgMaxLds && (!ox || r <= kPcgMaxR); };
@@ -1902,6 +1904,11 @@ int run(const m3s_gn_args& a) {
         g_dbg_pcg[2] = hf[kFlagPcgFall];
         g_dbg_pcg[3] = c.sp.pcg ? 1 : 0;
         g_dbg_pcg[4] = c.sp.pcg ? c.sp.pcg_from : 0;
+        g_dbg_pcg_plan[0] = c.sp.pcg ? c.sp.pcg_R : 0;
+        g_dbg_pcg_plan[1] = c.sp.pcg ? c.sp.pcg_nwg : 0;
+        g_dbg_pcg_plan[2] = c.sp.pcg && c.sp.pcg_onex ? 1 : 0;
+        g_dbg_pcg_plan[3] = c.sp.pcg ? c.sp.pcg_lag : 0;
+        g_dbg_pcg_plan[4] = c.sp.pcg ? c.sp.pcg_nitem : 0;
         if (dbg != 2)
             fprintf(stderr, "gn flags: done %d fail %d not_ray %d timeout %d packed %d pcg runs %d steps %d fallbacks %d\n",
                     hf[kFlagDone], hf[kFlagFail], hf[kFlagNotRay], hf[kFlagTimeout], (int)c.packed,
@@ -1932,6 +1939,10 @@ extern "C" void m3s_gn_debug_flags(int* out4) {
 
 extern "C" void m3s_gn_pcg_stats(int* out5) {
     for (int k = 0; k < 5; k++) out5[k] = m3s::g_dbg_pcg[k];
+}
+
+extern "C" void m3s_gn_pcg_plan(int* out5) {
+    for (int k = 0; k < 5; k++) out5[k] = m3s::g_dbg_pcg_plan[k];
 }
 
 extern "C" const char* m3s_version(void) { return "m3s 0.1.0 gfx950"; }

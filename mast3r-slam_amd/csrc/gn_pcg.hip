@@ -281,7 +281,9 @@ __global__ __launch_bounds__(NTH) void sp_inverse_kernel(InvArgs a) {
         __syncthreads();
         for (int id = tid; id < T * ICB; id += NTH) {
             const int cc = id / T, rr = id % T;
-            if (r0 + rr < n) a.Xt[(int64_t)(blockIdx.x * ICB + cc) * a.ldt + r0 + rr] = St[cc * (T + 1) + rr];
+            // (the last workgroup's columns past n are padding of X only: Xt has n rows)
+            if (r0 + rr < n && blockIdx.x * ICB + cc < n)
+                a.Xt[(int64_t)(blockIdx.x * ICB + cc) * a.ldt + r0 + rr] = St[cc * (T + 1) + rr];
         }
         __syncthreads();
     }
@@ -385,6 +387,12 @@ __global__ __launch_bounds__(PTH) void pcg_kernel(PcgArgs a) {
         int i = 0;
         while (sib[i + 1] <= it) i++;
         const int e = row0 + i, pr = e / 7, d = e - 7 * pr;
+        // ASSUMES symmetric 7x7 blocks: a pair's one stored block serves both of its poses, so
+        // the second pose's row d reads the block's row d where A has its column d (the
+        // transpose).  Every residual model gives blocks +-D with D symmetric (Ji = -Jj,
+        // gn_refacc.hip header) up to the accumulate's rounding; tests/test_gpu_pcg_solves.py
+        // pins the product per solve for rays, points and calib against a host CG on the
+        // assembled dense system.
         const int2 bs = a.adj[a.adj_ptr[pr] + (it - sib[i])];
         sps[it] = 7 * bs.y;
         const double* Ab = a.A + (int64_t)bs.x * 49 + d * 7;
@@ -404,8 +412,10 @@ __global__ __launch_bounds__(PTH) void pcg_kernel(PcgArgs a) {
     if (onex) {
         // B = M A, this workgroup's rows: column c = 7 pj + d of B is sum over the blocks (pk, pj)
         // of M's columns 7 pk .. 7 pk + 6 times the block's column d (the blocks are symmetric:
-        // Ji = -Jj makes every 7x7 block +-D with D symmetric, gn_refacc.hip header).  One thread
-        // per column, the R rows in registers, f64 sums rounded once to f32.
+        // Ji = -Jj makes every 7x7 block +-D with D symmetric, gn_refacc.hip header -- the same
+        // assumption as apply_A's staging above: a block that is not symmetric would make B the
+        // product with another matrix than the one q = A p uses).  One thread per column, the R
+        // rows in registers, f64 sums rounded once to f32.
         __syncthreads();  // (Xs staged)
         for (int col = tid; col < n; col += PTH) {
             const int pj = col / 7, d = col - 7 * pj;

@@ -678,14 +678,18 @@ def gn_check(device=None):
 def gn_debug_flags() -> dict:
     """Diagnostics of the last Gauss-Newton call made with env M3S_GN_DEBUG_FLAGS set (that call
     reads its device flags back): the accumulate path it took and its lagged-factor PCG solves
-    (include/m3s_backend.h m3s_gn_debug_flags / m3s_gn_pcg_stats)."""
+    (include/m3s_backend.h m3s_gn_debug_flags / m3s_gn_pcg_stats / m3s_gn_pcg_plan: the PCG's
+    rows per workgroup, workgroups, onex, lag and item capacity, 0 when none was planned)."""
     f = (ctypes.c_int * 4)()
     lib.m3s_gn_debug_flags(f)
     q = (ctypes.c_int * 5)()
     lib.m3s_gn_pcg_stats(q)
+    pl = (ctypes.c_int * 5)()
+    lib.m3s_gn_pcg_plan(pl)
     return {"done": f[0], "fail": f[1], "packed": bool(f[2]), "ray_constrained": bool(f[3]),
             "pcg_planned": bool(q[3]), "pcg_runs": q[0], "pcg_steps": q[1], "pcg_fallbacks": q[2],
-            "pcg_from": q[4]}
+            "pcg_from": q[4], "pcg_R": pl[0], "pcg_nwg": pl[1], "pcg_onex": pl[2], "pcg_lag": pl[3],
+            "pcg_nitem": pl[4]}
 
 
 def version() -> str:
