@@ -396,6 +396,50 @@ enum { M3S_FILTER_WEIGHTED_POINTMAP = 0, M3S_FILTER_INDEP_CONF = 1, M3S_FILTER_R
 int m3s_pointmap_update(int mode, const float* T, const float* X_new, const float* C_new,
                         float* X, float* C, int64_t HW, void* stream);
 
+/* ---------------- loop-closure retrieval (ASMK) ---------------- */
+
+/*
+ * RetrievalDatabase.update after the retrieval network (retrieval_database.py:43-166 with
+ * asmk/kernel.py:26-68, inverted_file.py:56-108, functional.py:11-15, hamming.pyx): binary kernel,
+ * no idf.  All on `stream`; a database is used from one stream at a time.  Extension ops (the
+ * reference runs this in torch, numpy and Cython on the host).
+ *
+ * create: centroids [K,D] f32 on the device, BORROWED (they must outlive the database);
+ *   1 <= D <= 4096, ma_build <= ma_query <= 8, K >= ma_query, max_feat * ma_query <= 4096.  |c|^2 is
+ *   computed here.  table_or_null: NULL for the library's term table (m3s_retrieval_term_table),
+ *   or [32 W + 1] f32 (host or device), W = ceil(D/32), the caller's own T[h] -- e.g. a host's
+ *   np.power values, to reproduce that host's scores bit for bit.
+ */
+int m3s_retrieval_create(const float* centroids, int64_t K, int64_t D, int ma_build, int ma_query,
+                         float alpha, float sim_thresh, const float* table_or_null,
+                         int64_t max_feat, void** db);
+int m3s_retrieval_destroy(void* db);
+int m3s_retrieval_size(void* db, int64_t* n_images);
+/* Host only (no GPU): T[h], h = 0..32W, the score term of a word pair at Hamming distance h:
+ * nh = (float)h / (float)(32 W); sim = -2 nh + 1 (f32); T = 0 where sim < sim_thresh, else the
+ * f32 rounding of pow((double)sim, (double)alpha).  table_out: host [32 W + 1]. */
+int m3s_retrieval_term_table(int64_t D, float alpha, float sim_thresh, float* table_out);
+/* ids_out [n,ma] i32: per feature the ma centroids of least |q|^2 + |c|^2 - 2 q.c (f32, the dot
+ * product on the f32-input MFMA), ascending; equal distances by the lower index.  1 <= ma <= 8. */
+int m3s_retrieval_quantize(void* db, const float* feat, int64_t n, int ma, int32_t* ids_out,
+                           void* stream);
+/* ids [n,ma] -> words_out [n*ma] i32 (the first *n_words_out ascending), codes_out [n*ma, W] u32
+ * (sign bits of the per-word f32 residual sums, MSB first), n_words_out [1] i32, all device. */
+int m3s_retrieval_aggregate(void* db, const float* feat, const int32_t* ids, int64_t n, int ma,
+                            int32_t* words_out, uint32_t* codes_out, int32_t* n_words_out,
+                            void* stream);
+/* Quantise (ma_query), aggregate and score against every stored image: scores_out [n_images] f64
+ * on the device (unused when the database is empty).  Keeps the query's nearest words for a
+ * following add of the same `feat`.  No host synchronisation. */
+int m3s_retrieval_query(void* db, const float* feat, int64_t n, double* scores_out, void* stream);
+/* Append the image: its ma_build nearest words per feature (those of the preceding
+ * m3s_retrieval_query of the same feat, n when reuse_last_query; else quantised here). */
+int m3s_retrieval_add(void* db, const float* feat, int64_t n, int reuse_last_query, void* stream);
+/* Read-back of stored image m (test / inspection): words_out [max_feat*ma_build] i32, codes_out
+ * [max_feat*ma_build, W] u32, n_words_out [1] i32, all device. */
+int m3s_retrieval_image(void* db, int64_t m, int32_t* words_out, uint32_t* codes_out,
+                        int32_t* n_words_out, void* stream);
+
 /* ---------------- multi-GPU (RCCL over xGMI) ---------------- */
 
 /*

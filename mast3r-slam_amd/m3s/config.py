@@ -1,6 +1,7 @@
 """Hot-path parameters of the reference configuration (values only).
 
-Source: /root/reference/config/base.yaml:8-14 (matching), :16-33 (tracking), :35-50 (local_opt);
+Source: /root/reference/config/base.yaml:8-14 (matching), :16-33 (tracking), :35-50 (local_opt),
+:52-58 (retrieval, reloc);
 calib.yaml:1-6 switches ``use_calib`` on.  ``load_config`` reads the reference's YAML
 format (``inherit:`` chaining, floats like ``1e-8``) with a SafeLoader, like
 mast3r_slam/config.py:7-48.
@@ -57,6 +58,14 @@ DEFAULT_CONFIG = {
         "sigma_point": 0.05,
         "delta_norm": 1e-8,
         "use_cuda": True,
+    },
+    "retrieval": {  # base.yaml:52-54
+        "k": 3,
+        "min_thresh": 5e-3,
+    },
+    "reloc": {  # base.yaml:56-58
+        "min_match_frac": 0.3,
+        "strict": True,
     },
 }
 

@@ -29,6 +29,16 @@ __all__ = [
     "CholeskyError",
     "pointmap_update",
     "edge_confidence",
+    "RetrievalHandle",
+    "retrieval_create",
+    "retrieval_destroy",
+    "retrieval_size",
+    "retrieval_term_table",
+    "retrieval_quantize",
+    "retrieval_aggregate",
+    "retrieval_query",
+    "retrieval_add",
+    "retrieval_image",
     "gn_plan_info",
     "library_path",
     "set_gn_order",
@@ -665,6 +675,188 @@ def pointmap_update(mode, X, C, X_new, C_new, T=None):
                                      _ptr(C), HW, _stream(dev))
     _raise(rc, "pointmap_update")
     return X, C
+
+# ---------------------------------------------------------------------------------
+# loop-closure retrieval (extension: retrieval_database.py:43-166 runs in torch / numpy / Cython)
+# ---------------------------------------------------------------------------------
+
+lib.m3s_retrieval_create.argtypes = [_vp, _c_int64, _c_int64, _i, _i, _f, _f, _vp, _c_int64,
+                                     ctypes.POINTER(_vp)]
+lib.m3s_retrieval_destroy.argtypes = [_vp]
+lib.m3s_retrieval_size.argtypes = [_vp, ctypes.POINTER(_c_int64)]
+lib.m3s_retrieval_term_table.argtypes = [_c_int64, _f, _f, _vp]
+lib.m3s_retrieval_quantize.argtypes = [_vp, _vp, _c_int64, _i, _vp, _vp]
+lib.m3s_retrieval_aggregate.argtypes = [_vp, _vp, _vp, _c_int64, _i, _vp, _vp, _vp, _vp]
+lib.m3s_retrieval_query.argtypes = [_vp, _vp, _c_int64, _vp, _vp]
+lib.m3s_retrieval_add.argtypes = [_vp, _vp, _c_int64, _i, _vp]
+lib.m3s_retrieval_image.argtypes = [_vp, _c_int64, _vp, _vp, _vp, _vp]
+
+RETRIEVAL_MA_MAX = 8       # largest multiple assignment
+RETRIEVAL_PAIRS_MAX = 4096  # max_feat * ma_query one aggregate sorts
+
+
+class RetrievalHandle:
+    """A device retrieval database (include/m3s_backend.h m3s_retrieval_*).  Holds the centroid
+    tensor, which the library borrows."""
+
+    def __init__(self, ptr, centroids, ma_build, ma_query, max_feat):
+        self.ptr = ptr
+        self.centroids = centroids
+        self.K, self.D = centroids.shape
+        self.W = (self.D + 31) // 32
+        self.ma_build, self.ma_query, self.max_feat = ma_build, ma_query, max_feat
+        self.device = centroids.device
+
+    def close(self):
+        if self.ptr is not None:
+            with torch.cuda.device(self.device):
+                lib.m3s_retrieval_destroy(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        import sys
+
+        if not sys.is_finalizing():
+            self.close()
+
+
+def retrieval_term_table(D, alpha, sim_thresh):
+    """The library's term table T[h], h = 0..32*ceil(D/32), as a numpy f32 array (host only)."""
+    import numpy as np
+
+    D = int(D)
+    if not 1 <= D <= 4096:
+        raise RuntimeError(f"retrieval_term_table: D = {D} outside 1..4096")
+    out = np.zeros(32 * ((D + 31) // 32) + 1, dtype=np.float32)
+    _raise(lib.m3s_retrieval_term_table(D, float(alpha), float(sim_thresh), out.ctypes.data),
+           "retrieval_term_table")
+    return out
+
+
+def retrieval_create(centroids, ma_build=1, ma_query=5, alpha=3.0, sim_thresh=0.0, table=None,
+                     max_feat=300):
+    """Create a database over ``centroids`` [K,D] f32 (kept by the handle).  ``table``: optional
+    [32*ceil(D/32)+1] f32 term table replacing the library's (numpy array or tensor)."""
+    _check(centroids, "centroids", torch.float32, 2)
+    K, D = centroids.shape
+    ma_build, ma_query, max_feat = int(ma_build), int(ma_query), int(max_feat)
+    if not 1 <= D <= 4096:
+        raise RuntimeError(f"retrieval_create: D = {D} outside 1..4096")
+    if not 1 <= ma_build <= ma_query <= RETRIEVAL_MA_MAX:
+        raise RuntimeError("retrieval_create: need 1 <= ma_build <= ma_query <= "
+                           f"{RETRIEVAL_MA_MAX}, got {ma_build}, {ma_query}")
+    if K < ma_query:
+        raise RuntimeError(f"retrieval_create: K = {K} is smaller than the multiple assignment {ma_query}")
+    if max_feat < 1 or max_feat * ma_query > RETRIEVAL_PAIRS_MAX:
+        raise RuntimeError(f"retrieval_create: max_feat * ma_query = {max_feat * ma_query} outside "
+                           f"1..{RETRIEVAL_PAIRS_MAX}")
+    tab = None
+    if table is not None:
+        tab = torch.as_tensor(table).detach().to(device="cpu", dtype=torch.float32).contiguous()
+        if tab.dim() != 1 or tab.numel() != 32 * ((D + 31) // 32) + 1:
+            raise RuntimeError(f"retrieval_create: table must hold {32 * ((D + 31) // 32) + 1} floats")
+    dev = _on_device(centroids=centroids)
+    out = _vp()
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()  # the centroids are read on the null stream
+        rc = lib.m3s_retrieval_create(_ptr(centroids), K, D, ma_build, ma_query, float(alpha),
+                                      float(sim_thresh), _ptr(tab), max_feat, ctypes.byref(out))
+    _raise(rc, "retrieval_create")
+    return RetrievalHandle(out, centroids, ma_build, ma_query, max_feat)
+
+
+def retrieval_destroy(db):
+    db.close()
+
+
+def _retrieval_feat(db, feat, what):
+    if not isinstance(db, RetrievalHandle) or db.ptr is None:
+        raise RuntimeError(f"{what}: not an open retrieval database")
+    _check(feat, "feat", torch.float32, 2)
+    n, D = feat.shape
+    if D != db.D:
+        raise RuntimeError(f"{what}: feat has D = {D}, the codebook {db.D}")
+    if not 1 <= n <= db.max_feat:
+        raise RuntimeError(f"{what}: n = {n} outside 1..max_feat = {db.max_feat}")
+    dev = _on_device(feat=feat)
+    if dev != db.device:
+        raise RuntimeError(f"{what}: feat must be on {db.device}, got {dev}")
+    return dev, n
+
+
+def retrieval_size(db):
+    n = _c_int64()
+    _raise(lib.m3s_retrieval_size(db.ptr, ctypes.byref(n)), "retrieval_size")
+    return int(n.value)
+
+
+def retrieval_quantize(db, feat, ma):
+    """-> ids [n,ma] int32: the ma nearest centroids per feature, ascending distance, ties by the
+    lower index."""
+    dev, n = _retrieval_feat(db, feat, "retrieval_quantize")
+    ma = int(ma)
+    if not 1 <= ma <= min(RETRIEVAL_MA_MAX, db.K):
+        raise RuntimeError(f"retrieval_quantize: ma = {ma} outside 1..{min(RETRIEVAL_MA_MAX, db.K)}")
+    ids = torch.empty((n, ma), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.m3s_retrieval_quantize(db.ptr, _ptr(feat), n, ma, _ptr(ids), _stream(dev))
+    _raise(rc, "retrieval_quantize")
+    return ids
+
+
+def retrieval_aggregate(db, feat, ids):
+    """ids [n,ma] int32 -> (words [n*ma] int32, codes [n*ma,W] int32 bit patterns, n_words [1]
+    int32); the first n_words rows are valid, words ascending."""
+    dev, n = _retrieval_feat(db, feat, "retrieval_aggregate")
+    _check(ids, "ids", torch.int32, 2)
+    _on_device(feat=feat, ids=ids)
+    ma = ids.shape[1]
+    if ids.shape[0] != n or not 1 <= ma <= db.ma_query:
+        raise RuntimeError(f"retrieval_aggregate: ids must be [n, 1..{db.ma_query}]")
+    words = torch.zeros((n * ma,), dtype=torch.int32, device=dev)
+    codes = torch.zeros((n * ma, db.W), dtype=torch.int32, device=dev)
+    count = torch.zeros((1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.m3s_retrieval_aggregate(db.ptr, _ptr(feat), _ptr(ids), n, ma, _ptr(words),
+                                         _ptr(codes), _ptr(count), _stream(dev))
+    _raise(rc, "retrieval_aggregate")
+    return words, codes, count
+
+
+def retrieval_query(db, feat):
+    """-> scores [n_images] f64 on the device (empty for an empty database)."""
+    dev, n = _retrieval_feat(db, feat, "retrieval_query")
+    scores = torch.empty((retrieval_size(db),), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.m3s_retrieval_query(db.ptr, _ptr(feat), n, _ptr(scores), _stream(dev))
+    _raise(rc, "retrieval_query")
+    return scores
+
+
+def retrieval_add(db, feat, reuse_last_query=False):
+    """Append the image of ``feat``; ``reuse_last_query`` takes the nearest words of the
+    retrieval_query just made with the same tensor."""
+    dev, n = _retrieval_feat(db, feat, "retrieval_add")
+    with torch.cuda.device(dev):
+        rc = lib.m3s_retrieval_add(db.ptr, _ptr(feat), n, int(bool(reuse_last_query)), _stream(dev))
+    _raise(rc, "retrieval_add")
+
+
+def retrieval_image(db, m):
+    """Stored image m -> (words [n_words] int32, codes [n_words,W] int32 bit patterns) on the
+    device (synchronises to read n_words)."""
+    if not isinstance(db, RetrievalHandle) or db.ptr is None:
+        raise RuntimeError("retrieval_image: not an open retrieval database")
+    dev = db.device
+    row = db.max_feat * db.ma_build
+    words = torch.empty((row,), dtype=torch.int32, device=dev)
+    codes = torch.empty((row, db.W), dtype=torch.int32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.m3s_retrieval_image(db.ptr, int(m), _ptr(words), _ptr(codes), _ptr(count), _stream(dev))
+    _raise(rc, "retrieval_image")
+    k = int(count.item())
+    return words[:k], codes[:k]
 
 
 def gn_check(device=None):
