@@ -1417,13 +1417,7 @@ hipError_t launch_chol_dataflow(hipStream_t st, int npad, double* Hd, double* Li
     // exit-time fault of a process that made a cooperative launch (profiles/r03_exit_fault).  The
     // dynamic task claim needs no co-residency: should the device not hold the whole grid
     // (another stream's kernels occupying CUs), the late workgroups only claim later tickets; the
-    // bounded waits remain a hang guard (M3S_ERR_TIMEOUT).  M3S_CHOL_COOP=1: cooperative.
-    static const bool coop = [] {
-        const char* e = getenv("M3S_CHOL_COOP");
-        return e && atoi(e) != 0;
-    }();
-    void* kargs[] = {&a};
-    if (coop) return hipLaunchCooperativeKernel((const void*)chol_df_kernel, dim3(grid), dim3(NT), kargs, 0, st);
+    // bounded waits remain a hang guard (M3S_ERR_TIMEOUT).
     hipLaunchKernelGGL(chol_df_kernel, dim3(grid), dim3(NT), 0, st, a);
     return hipGetLastError();
 }

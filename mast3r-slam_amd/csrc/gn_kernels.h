@@ -22,9 +22,8 @@ constexpr int kFlagDone = 0;   // set once ||dx|| < delta_thresh (skips later it
 constexpr int kFlagFail = 1;   // set by the factorisation when a pivot <= 0
 constexpr int kFlagNotRay = 2; // calib: some Xs point is not its pixel's ray times its depth
 constexpr int kFlagTimeout = 3; // sticky for the call: a bounded device-side wait gave up (chol_df
-                                // ready word, grid barrier); the driver returns M3S_ERR_TIMEOUT
-constexpr int kFlagBarCount = 4;  // grid barrier of the all-rounds launch: arrivals
-constexpr int kFlagBarGen = 5;    // ... and its generation
+                                // ready word, round ticket); the driver returns M3S_ERR_TIMEOUT
+// (4 and 5 are reserved: unused slots)
 // The lagged-factor PCG (gn_pcg.hip) of an iteration that converged has retracted the poses
 // itself; the direct solve's launches enqueued behind it (its fallback) then return at once
 // (solve_skipped).  Set or cleared by every PCG launch; never set in iterations without one.
@@ -170,27 +169,25 @@ hipError_t launch_dense_factor_solve(hipStream_t st, int npad, double* Hd, doubl
 hipError_t launch_sp_tail_scatter(hipStream_t st, const double* xd, const int* tail, int ntail, double* x,
                                   const int* flags);
 // multi-launch block-sparse elimination (gn_sparse.hip): one launch per round
-// every elimination round (+ optionally the hybrid core's dense fill) in one cooperative launch
 // Per round target, one record of kSpRec ints: {target, c0, c1, 0} then the first kSpInline
 // contributions {v, code_r, code_s | W id, 0 | owner} inline (the rest from tc3 / rc4), so a
 // workgroup's plan arrives in ONE load round trip with the flag.  Round rd's records start at
 // tbeg + rbeg (its block targets, then its RHS targets).
 constexpr int kSpInline = 9;
 constexpr int kSpRec = 4 + 4 * kSpInline;
-struct SpCoopArgs {
+struct SpRoundsArgs {
     const int *inl, *tc3, *rc4, *rounds, *tmap, *tail;
-    double *A, *b, *Lstore, *W, *y, *Hd;
+    double *A, *b, *Lstore, *W, *y, *Hd;  // Hd != nullptr: the launch also fills the dense core
     int* flags;
     int nrounds, ntail, npad;
-    int coop;  // 1: cooperative-groups grid sync; 0: own barrier (both as a cooperative launch)
 };
-hipError_t launch_sp_rounds_coop(hipStream_t st, const SpCoopArgs& args);
-// The same rounds (and the hybrid core's fill) in one PLAIN launch without co-residency: the
-// workgroups claim (round, target) tickets in order from a counter and a target waits for the
-// previous round's completion count -- only ever on tickets running workgroups already hold.
+// Every elimination round (and optionally the dense core's fill) in one PLAIN launch without
+// co-residency: the workgroups claim (round, target) tickets in order from a counter and a target
+// waits for the previous round's completion count -- only ever on tickets running workgroups
+// already hold.
 // cnt: 4 + nrounds ints zeroed once (ticket, exits, spare, spare, per-round done counts); the last
 // workgroup out re-zeroes them.  (gn_sparse.hip sp_rounds_df_kernel)
-hipError_t launch_sp_rounds_df(hipStream_t st, const SpCoopArgs& args, int* cnt);
+hipError_t launch_sp_rounds_df(hipStream_t st, const SpRoundsArgs& args, int* cnt);
 inline int sp_rounds_df_words(int nrounds) { return (4 + nrounds + 31) / 32 * 32; }
 hipError_t launch_sp_round(hipStream_t st, const int* inl, int ibeg, int nbt, int nrt, const int* tc3,
                            const int* rc4, double* A, double* b, double* Lstore, double* W, double* y,
@@ -299,7 +296,7 @@ hipError_t launch_gn_solve(hipStream_t st, const SolveArgs& args);
 // copy `bytes` (a multiple of 4; both addresses 16-B aligned) from pinned host memory (its
 // device address) to device memory, stream-ordered, by a kernel
 hipError_t launch_stage_copy(hipStream_t st, void* dst, const void* src_dev, size_t bytes);
-// The accumulate's task records {edge, chunk, ix, jx} from the host's edge order (gn_driver.hip
+// The accumulate's task records {edge, chunk, ix, jx} from the host's edge order (gn_plan.hip
 // build_schedule_order): edge-major (off) or 8 XCD groups interleaved round-robin, each group's
 // list chunk-major -- expanded on the device instead of written record by record into pinned
 // memory and read back over PCIe.

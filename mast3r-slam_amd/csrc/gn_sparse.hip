@@ -3,7 +3,7 @@
 // The GN system is a graph Laplacian with 7x7 blocks, in the block format of
 // gn_assemble_kernel: b (npose x 7), then one 49-f64 row-major block per pose and per
 // co-observing pose pair (block (x, y), x < y, holds the rows of pose x; fill blocks zeroed).
-// The driver (gn_driver.hip, build_sparse_plan) picks, round by round, an independent set V of
+// The driver (gn_plan.hip, build_sparse_plan) picks, round by round, an independent set V of
 // low-degree poses.  A round eliminates all of V in ONE launch, one workgroup per target:
 //   block target (r, s):  A_rs -= sum_{v in V} W_rv W_sv^T
 //   RHS target r:         b_r  -= sum_{v in V} W_rv y_v
@@ -21,7 +21,6 @@
 // integers, then the blocks): a dependent global round trip is the unit of cost here.
 // Failure semantics follow SimplicialLLT (reference gn_kernels.cu:142-150): a pivot <= 0 sets
 // the failure flag and the update becomes zero.
-#include <hip/hip_cooperative_groups.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,10 +43,10 @@ static_assert(kSpInline == kGroups, "a target record inlines one contribution pe
 // owner node | -1) for RHS targets; code = block * 2 + transposed (the block holds the rows of
 // the other pose).  r = -1 collects the poses without fronts: only their L and y are stored.
 // The first kSpInline contributions ride in the record, the rest come from tc3 / rc4.
-// COH: the all-rounds launch reads, in round r + 1, blocks other workgroups (other XCDs) wrote
-// in round r.  The per-XCD L2s are not coherent, so those A / b accesses are agent-coherent
-// (relaxed agent-scope atomics: sc1 loads and write-through stores) and the grid barrier needs
-// no L2 write-back or invalidation.
+// COH: the ticketed all-rounds launch (sp_rounds_df_kernel) reads, in round r + 1, blocks other
+// workgroups (other XCDs) wrote in round r.  The per-XCD L2s are not coherent, so those A / b
+// accesses are agent-coherent (relaxed agent-scope atomics: sc1 loads and write-through stores)
+// and a round's done count needs no L2 write-back or invalidation.
 template <bool COH>
 __device__ __forceinline__ double ldA(const double* p) {
     if constexpr (COH) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -260,80 +259,18 @@ __global__ __launch_bounds__(256) void sp_tail_fill_kernel(const double* __restr
     sp_tail_fill<false>(A, b, tmap, tail, ntail, npad, Hd);
 }
 
-// All elimination rounds (and the hybrid's core fill) in ONE cooperative launch: a round costs
-// ~4 us of dependent work per workgroup (target record ~1, block loads ~1.4, 7x7 factor + W rows
-// ~1, Schur sums + store ~0.4, measured in-kernel) but ~9 us as its own launch, the rest being
-// the dependent launch's dispatch and drain.  Here a grid-wide barrier (cooperative groups,
-// co-residency guaranteed by hipLaunchCooperativeKernel) separates the rounds; workgroup w takes
-// the round's targets w, w + G, ...  The flag is read once: it was written by the previous
-// iteration's kernels, so every workgroup sees the same value and all leave or none.
-// Grid-wide barrier over the launch's workgroups (all resident: <= one 64-thread workgroup per
-// CU): arrival counter + generation word in the flags area.  Release = the arrival atomic
-// (writes back this XCD's L2), acquire = a fence after the generation moved (invalidates L1/L2),
-// so blocks written in one round are read fresh in the next on any XCD.  The spin is bounded
-// (~0.1 s): a workgroup that never arrives fails the solve and raises the sticky timeout flag
-// (reported by the driver as M3S_ERR_TIMEOUT) instead of hanging the GPU; the caller then
-// leaves the launch (the arrival counter is no longer consistent).
-template <bool FENCED>
-__device__ __forceinline__ void grid_barrier(int* __restrict__ flags, unsigned nwg) {
-    if constexpr (!FENCED) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my write-through stores landed
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned* cnt = reinterpret_cast<unsigned*>(flags + kFlagBarCount);
-        unsigned* gen = reinterpret_cast<unsigned*>(flags + kFlagBarGen);
-        const unsigned g = __hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned old = FENCED ? __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT)
-                                    : __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == nwg - 1) {
-            __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(gen, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            int spins = 0;
-            while (__hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1 << 22)) {
-                    __hip_atomic_store(flags + kFlagTimeout, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(flags + kFlagFail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    break;
-                }
-            }
-        }
-        if constexpr (FENCED) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(64) void sp_rounds_coop_kernel(SpCoopArgs a) {
-    __shared__ double sR[kGroups][7 * kLd];
-    __shared__ double sS[kGroups][7 * kLd];
-    if (solve_skipped(a.flags)) return;
-    for (int rd = 0; rd < a.nrounds; rd++) {
-        const int* R = a.rounds + 8 * rd;  // node_begin, nnodes, tbeg, nbt, rbeg, nrt, wbeg, wcount
-        const int tbeg = R[2], nbt = R[3], rbeg = R[4], nrt = R[5];
-        for (int t = blockIdx.x; t < nbt + nrt; t += gridDim.x)
-            sp_round_target<true>(a.inl + (int64_t)(tbeg + rbeg + t) * kSpRec, t < nbt, a.tc3, a.rc4, nullptr,
-                                  a.A, a.b, a.Lstore, a.W, a.y, a.flags, sR, sS);
-        if (a.coop) {
-            cooperative_groups::this_grid().sync();
-        } else {
-            grid_barrier<false>(a.flags, gridDim.x);
-            // a timed-out barrier leaves the arrival counter inconsistent: abandon the launch
-            // (every workgroup reaches this test after its own barrier wait)
-            if (__hip_atomic_load(a.flags + kFlagTimeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-        }
-    }
-    if (a.ntail > 0 && a.Hd) sp_tail_fill<true>(a.A, a.b, a.tmap, a.tail, a.ntail, a.npad, a.Hd);
-}
-
-// The rounds without a grid barrier or co-residency (launch_sp_rounds_df, gn_kernels.h): the
-// (round, target) pairs are tickets in round order, then the core fill in chunks of kDfFill
-// entries; a workgroup claims the next ticket, waits (one lane, bounded) for the previous round's
-// done count (the fill: the last round's), runs it with the coherent block accesses of the
-// all-rounds launch and bumps its round's count after its stores landed.  Every wait is on tickets
+// All elimination rounds (and the core's fill) in ONE launch, without a grid barrier or
+// co-residency (launch_sp_rounds_df, gn_kernels.h): a round costs ~4 us of dependent work per
+// workgroup (target record ~1, block loads ~1.4, 7x7 factor + W rows ~1, Schur sums + store ~0.4,
+// measured in-kernel) but ~9 us as its own launch, the rest being the dependent launch's dispatch
+// and drain.  The (round, target) pairs are tickets in round order, then the core fill in chunks
+// of kDfFill entries; a workgroup claims the next ticket, waits (one lane, bounded) for the
+// previous round's done count (the fill: the last round's), runs it with coherent block accesses
+// (COH above) and bumps its round's count after its stores landed.  Every wait is on tickets
 // that running workgroups hold, so any resident subset progresses; a workgroup's target does not
 // change the arithmetic (bitwise the per-round launches).
 constexpr int kDfFill = 4096;
-__global__ __launch_bounds__(64) void sp_rounds_df_kernel(SpCoopArgs a, int* __restrict__ cnt) {
+__global__ __launch_bounds__(64) void sp_rounds_df_kernel(SpRoundsArgs a, int* __restrict__ cnt) {
     __shared__ double sR[kGroups][7 * kLd];
     __shared__ double sS[kGroups][7 * kLd];
     __shared__ int s_tk;
@@ -427,26 +364,7 @@ hipError_t launch_sp_round(hipStream_t st, const int* inl, int ibeg, int nbt, in
     return hipGetLastError();
 }
 
-hipError_t launch_sp_rounds_coop(hipStream_t st, const SpCoopArgs& args) {
-    if (args.nrounds <= 0 && (args.ntail <= 0 || !args.Hd)) return hipSuccess;
-    static int grid = 0;
-    if (grid == 0) {
-        int dev = 0, ncu = 0, per = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e == hipSuccess)
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)sp_rounds_coop_kernel, 64, 0);
-        if (e != hipSuccess) return e;
-        grid = std::max(1, std::min(ncu * std::max(per, 1), 256));  // <= one workgroup per CU
-    }
-    // both barrier flavours need every workgroup resident at once: always a cooperative launch
-    // (it refuses a grid the device cannot hold); `coop` only picks the barrier implementation
-    SpCoopArgs a = args;
-    void* kargs[] = {&a};
-    return hipLaunchCooperativeKernel((const void*)sp_rounds_coop_kernel, dim3(grid), dim3(64), kargs, 0, st);
-}
-
-hipError_t launch_sp_rounds_df(hipStream_t st, const SpCoopArgs& args, int* cnt) {
+hipError_t launch_sp_rounds_df(hipStream_t st, const SpRoundsArgs& args, int* cnt) {
     if (args.nrounds <= 0 && (args.ntail <= 0 || !args.Hd)) return hipSuccess;
     // one 64-thread workgroup per CU at most (M3S_SOLVE_DF_WG): the widest round has ~500 targets
     static int grid = 0;

@@ -1,8 +1,8 @@
 // sparse_plan.h -- host-side block-sparse elimination plan of the GN solve (gn_sparse.hip runs
 // it): rounds of independent low-degree poses, then a dense core (chol_df.hip / gn_solve.hip).
 // Built once per GN call from the pose graph (fixed across the call's iterations), on every rank.
-// Host-only code, kept apart from gn_driver.hip so that it builds and is timed without a GPU
-// (tools/plan_bench.cpp).  Replaces the reference's per-iteration SparseBlock assembly +
+// Host-only code, kept apart from the driver (gn_plan.hip) so that it builds and is timed without
+// a GPU (tools/plan_bench.cpp).  Replaces the reference's per-iteration SparseBlock assembly +
 // SimplicialLLT analysis (gn_kernels.cu:57-159) with a plan the device solve replays.
 #pragma once
 
@@ -35,7 +35,7 @@ struct SparsePlan {
     int pcg_R = 0, pcg_nwg = 0, pcg_ldx = 0, pcg_ldt = 0, pcg_nv = 0, pcg_nitem = 0;
     size_t o_pcgx = 0, o_pcgxt = 0, o_gran = 0;
     // the factor the first inverse reads, copied out of the live one (Lstore .. Linv) when M comes
-    // from an earlier iteration than the one before the first PCG (gn_driver.hip pcg_lag)
+    // from an earlier iteration than the one before the first PCG (gn_plan.hip pcg_lag_for)
     size_t o_snap = 0, snap_bytes = 0;
     size_t o_dfcnt = 0;  // the ticketed all-rounds launch's counters (sp_rounds_df_words ints)
     int nblocks = 0, nW = 0, ntail = 0, npad_tail = 0, zero_blk = 0;

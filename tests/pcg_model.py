@@ -89,7 +89,7 @@ def rel_err(x, H, b):
 
 
 def lag_for(frm, lag):
-    """gn_driver.hip pcg_lag_for."""
+    """gn_plan.hip pcg_lag_for."""
     return max(1, min(frm, lag))
 
 
@@ -112,7 +112,7 @@ def call_policy(systems, frm, lag, onex=False, f32=True, kmax=KMAX, tol=TOL):
     return out
 
 
-# ---- choose_pcg's workgroup shape (gn_driver.hip choose_pcg, gn_pcg.hip pcg_lds_bytes) ----
+# ---- choose_pcg's workgroup shape (gn_plan.hip choose_pcg, gn_pcg.hip pcg_lds_bytes) ----
 PCG_MAX_N = 2304            # kPcgMaxN
 PCG_THREADS = 768           # kPcgThreads
 PCG_MAX_LDS = 160 * 1024 - 1024

@@ -106,7 +106,7 @@ def _gather_worker(rank, world, port, ranges, out_q):
     Hs, gs = O.gn_align(P, g.Twc.numpy(), g.Xs.numpy(), g.Cs.numpy(), ie[lo:hi], je[lo:hi],
                         g.idx.numpy()[lo:hi], g.valid.numpy()[lo:hi], g.Q.numpy()[lo:hi])
     # the op's default exchange: every rank's per-edge records (Hs [4, E, 7, 7], gs [2, E, 7]),
-    # gathered in blocks of the largest range (gn_driver.hip Plan::gather), then ALL edges
+    # gathered in blocks of the largest range (gn_host.h Plan::gather), then ALL edges
     # assembled in edge order on every rank
     n = hi - lo
     chunk = max(h - l for l, h in ranges)

@@ -20,7 +20,7 @@ from tests.test_gpu_gn import _rel, _run_gpu, _run_oracle
 
 pytestmark = pytest.mark.gpu
 
-# gn_driver.hip pcg_from_for: the first PCG iteration -- 3 on cores of >= 8 tile columns (cfg4's
+# gn_plan.hip pcg_from_for: the first PCG iteration -- 3 on cores of >= 8 tile columns (cfg4's
 # multi plan, 14), 4 below (cfg3's hybrid core, 4); M from two iterations earlier
 PCG_FROM = {"cfg3": 4, "cfg4": 3}
 
@@ -35,8 +35,9 @@ def _graph(cfg, H, W, seed=None):
 
 
 def _run(backend, monkeypatch, g, mode, iters, **env):
-    # (2: on every plan the inverse can read; the default, 1, leaves out plans whose dense core has
-    # fewer than M3S_PCG_MIN_TILES = 1 tile columns, i.e. none)
+    # (2: on every plan the inverse can read.  The default, 1, asks for a dense core of at least
+    # M3S_PCG_MIN_TILES = 1 tile columns, which every such plan has; the ">= 8 tile columns" of
+    # pcg_from_for only picks the first PCG iteration, PCG_FROM above)
     env.setdefault("M3S_GN_PCG", 2)
     for k, v in env.items():
         monkeypatch.setenv(k, str(v))
@@ -84,12 +85,23 @@ def test_pcg_runs_and_matches_the_direct_solve(backend, monkeypatch, cfg, H, W):
     assert np.array_equal(T_p2, T_p) and np.array_equal(dx_p2, dx_p)
 
 
-def test_pcg_fallback_is_bitwise_the_direct_solve(backend, monkeypatch):
-    """kmax = 1 CG step: no PCG solve converges, every iteration falls back to the direct
-    factorisation enqueued behind it -- bitwise the PCG-off call."""
-    g = _graph("cfg3", 48, 64)
-    T_d, dx_d, _ = _run(backend, monkeypatch, g, "calib", 6, M3S_GN_PCG=0)
-    # (kmax is read once per process: a child process)
+_DIRECT = {}  # (cfg, H, W) -> the in-process M3S_GN_PCG=0 poses (per-round launches), computed once
+
+
+@pytest.mark.parametrize("case", ["pcg_fallback", "direct_ticketed"])
+@pytest.mark.parametrize("cfg,H,W", [("cfg3", 48, 64), ("cfg4", 48, 64)])
+def test_pcg_fallback_is_bitwise_the_direct_solve(backend, monkeypatch, cfg, H, W, case):
+    """The ticketed rounds launch (sp_rounds_df_kernel) against one launch per round, on the hybrid
+    plan (cfg3) and on the multi plan (cfg4), where the ticketed launch also fills the core.
+    pcg_fallback: kmax = 1 CG step, no PCG solve converges, every iteration falls back to the
+    direct factorisation enqueued behind it (ticketed by default) -- bitwise the PCG-off call.
+    direct_ticketed: M3S_SOLVE_DF=2 with the PCG off, every direct solve ticketed -- bitwise the
+    same call with one launch per round."""
+    mode = synth.CONFIGS[cfg]["mode"]
+    if (cfg, H, W) not in _DIRECT:
+        _DIRECT[cfg, H, W] = _run(backend, monkeypatch, _graph(cfg, H, W), mode, 6, M3S_GN_PCG=0)[0]
+    T_d = _DIRECT[cfg, H, W]
+    # (kmax and M3S_SOLVE_DF are read once per process: a child process)
     import subprocess
     import sys
 
@@ -98,23 +110,28 @@ def test_pcg_fallback_is_bitwise_the_direct_solve(backend, monkeypatch):
         "import numpy as np, torch\n"
         "import mast3r_slam_backends as mb\n"
         "from tests import test_gpu_pcg as t\n"
-        "g = t._graph('cfg3', 48, 64)\n"
+        "g = t._graph(%r, %d, %d)\n"
         "from tests.test_gpu_gn import _run_gpu\n"
-        "T, dx = _run_gpu(mb, g, 'calib', 6)\n"
+        "T, dx = _run_gpu(mb, g, %r, 6)\n"
         "mb.gn_check()\n"
         "print('STATS', mb.gn_debug_flags())\n"
         "np.save(sys.argv[1], T)\n"
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-         os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mast3r-slam_amd"))
+         os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mast3r-slam_amd"),
+         cfg, H, W, mode)
     import tempfile
 
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "T.npy")
-        env = dict(os.environ, M3S_PCG_KMAX="1", M3S_GN_DEBUG_FLAGS="2", M3S_GN_PCG="2")
+        if case == "pcg_fallback":
+            env = dict(os.environ, M3S_PCG_KMAX="1", M3S_GN_DEBUG_FLAGS="2", M3S_GN_PCG="2")
+            n = 6 - PCG_FROM[cfg]
+        else:
+            env = dict(os.environ, M3S_SOLVE_DF="2", M3S_GN_DEBUG_FLAGS="2", M3S_GN_PCG="0")
+            n = 0
         r = subprocess.run([sys.executable, "-c", code, out], env=env, capture_output=True, text=True, timeout=240,
                            cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         assert r.returncode == 0, r.stderr[-2000:]
-        n = 6 - PCG_FROM["cfg3"]
         assert f"'pcg_runs': {n}" in r.stdout and f"'pcg_fallbacks': {n}" in r.stdout, r.stdout
         T_f = np.load(out)
     assert np.array_equal(T_f, T_d)

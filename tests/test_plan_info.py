@@ -1,4 +1,4 @@
-"""The GN solve's elimination plan (sparse_plan.h, chosen by gn_driver.hip choose_sparse_plan),
+"""The GN solve's elimination plan (sparse_plan.h, chosen by gn_plan.hip choose_sparse_plan),
 checked on the host through the diagnostic m3s_gn_plan_info -- no GPU.  The reference leaves this
 step to Eigen's SimplicialLLT symbolic analysis on every solve (gn_kernels.cu:132-153); here the
 plan is a sequence of rounds of independent poses plus a dense core, and the checks are the

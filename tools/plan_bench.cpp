@@ -1,6 +1,6 @@
 // plan_bench.cpp -- host-only timing of the GN elimination planner (sparse_plan.h) on a graph's
 // directed edge list, without a GPU.  Input (stdin): "N E" then E lines "ii jj" (global keyframe
-// ids, the op's ii/jj).  The pose pairs are formed exactly as gn_driver.hip's build_plan does
+// ids, the op's ii/jj).  The pose pairs are formed exactly as gn_plan.hip's build_plan does
 // (unique ids, first pose pinned, pairs in first-appearance order).
 //   hipcc -O2 -std=c++17 -I mast3r-slam_amd/csrc tools/plan_bench.cpp -o /tmp/plan_bench
 //   python tools/plan_graph.py cfg4 | /tmp/plan_bench
@@ -38,7 +38,7 @@ int main() {
         const char* name;
         RoundPolicy pol;
     };
-    // the driver's defaults (gn_driver.hip fused_policy / hybrid_policy / multi_policy)
+    // the driver's defaults (gn_plan.hip fused_policy / hybrid_policy / multi_policy)
     const P pols[] = {{"fused", {true, 64, 1, 64, kTailPoseMax, 4, true}},
                       {"hybrid", {false, 64, 1, 64, kTailPoseMax, 4, true}},
                       {"multi", {false, 32, 2, 64, 0, 0, false}}};
