@@ -396,6 +396,43 @@ enum { M3S_FILTER_WEIGHTED_POINTMAP = 0, M3S_FILTER_INDEP_CONF = 1, M3S_FILTER_R
 int m3s_pointmap_update(int mode, const float* T, const float* X_new, const float* C_new,
                         float* X, float* C, int64_t HW, void* stream);
 
+/* ---------------- map export ---------------- */
+
+/*
+ * The confidence-filtered world point cloud of N keyframes as the body of a binary little-endian
+ * PLY file (replaces save_reconstruction, evaluate.py:47-106; extension op -- the reference builds
+ * the cloud on the host).  For k = 0..N-1, n = 0..HW-1, in that order:
+ *   kept    C[k,n] / n_obs[k] > thresh       (f32 divide and compare; NaN is not kept)
+ *   point   p = X[k,n]; with K, p = z ((u - cx) / fx, (v - cy) / fy, 1), z = X[k,n,2],
+ *           u = n % width, v = n / width  (geometry.py:37-42, f32 subtract / divide / multiply);
+ *           pW = s R(q) p + t of T_WC[k]  (the act of m3s_pointmap_update, uncontracted)
+ *   record  <f4 x, f4 y, f4 z, u1 r, u1 g, u1 b>: 15 bytes, packed, little-endian
+ * count: counts [N] i64 = kept points per keyframe, total [1] i64 = their sum (both device); leaves
+ *   the tile offsets in ws.  emit: follows a count with the same args and ws on the same stream;
+ *   writes the first min(total, capacity) records to out and nothing past 15 * capacity bytes.
+ * Neither call synchronises the host.  N == 0 or HW == 0: M3S_OK, total 0.  Two runs give the
+ * same bytes.  A tile (m3s_recon_tile_points points) never spans two keyframes.
+ */
+typedef struct m3s_recon_args {
+  const float* X;      /* [N,HW,3] */
+  const float* C;      /* [N,HW] */
+  const float* n_obs;  /* [N] */
+  const float* T_WC;   /* [N,8] */
+  const uint8_t* rgb;  /* [N,HW,3] or NULL (records get 0,0,0) */
+  const float* K;      /* [3,3] device or NULL */
+  int64_t N, HW;
+  int height, width;   /* height*width == HW, used only with K */
+  float thresh;
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+} m3s_recon_args;
+size_t m3s_recon_workspace_bytes(int64_t N, int64_t HW);
+int64_t m3s_recon_tile_points(void);
+int m3s_recon_count(const m3s_recon_args* args, int64_t* counts /* [N] dev */,
+                    int64_t* total /* [1] dev */);
+int m3s_recon_emit(const m3s_recon_args* args, void* out /* dev, 15*capacity B */, int64_t capacity);
+
 /* ---------------- loop-closure retrieval (ASMK) ---------------- */
 
 /*

@@ -19,9 +19,11 @@ from .global_opt import PoseBatch
 
 
 class Frame:
-    def __init__(self, frame_id=0, img=None, T_WC=None, X_canon=None, C=None, K=None, cfg=None):
+    def __init__(self, frame_id=0, img=None, T_WC=None, X_canon=None, C=None, K=None, cfg=None,
+                 uimg=None):
         self.frame_id = frame_id
         self.img = img
+        self.uimg = uimg  # [H,W,3] f32 in [0,1] (frame.py:22), read by the map export
         self.T_WC = T_WC if T_WC is not None else PoseBatch(_identity())
         self.X_canon = X_canon
         self.C = C

@@ -45,6 +45,13 @@ class PoseBatch:
         return PoseBatch(self.data[k])
 
 
+def quantize_uimg(uimg):
+    """f32 image in [0,1] -> u8 as save_reconstruction does, ``(uimg * 255).astype(np.uint8)``
+    (evaluate.py:60): the product truncated.  Values outside [0,1] are clamped first (an
+    extension: the reference's cast is undefined there); NaN becomes 0."""
+    return torch.nan_to_num(uimg.to(torch.float32) * 255.0, nan=0.0).clamp_(0.0, 255.0).to(torch.uint8)
+
+
 class _KeyframeView:
     def __init__(self, store, i):
         self._s, self._i = store, i
@@ -61,6 +68,21 @@ class _KeyframeView:
     def img(self):
         return self._s.img_placeholder
 
+    @property
+    def frame_id(self):
+        return self._s.frame_ids[self._i]
+
+    @property
+    def uimg(self):
+        """The kept image as the reference holds it, [H,W,3] f32 in [0,1] (from the u8 copy)."""
+        if self._s.rgb is None:
+            raise AttributeError("uimg: the store was created with keep_rgb=False")
+        return self._s.rgb[self._i].reshape(self._s.h, self._s.w, 3).to(torch.float32) / 255.0
+
+    @property
+    def K(self):
+        return self._s.K
+
     def get_average_conf(self):
         return self._s.C[self._i] / self._s.n_obs[self._i]
 
@@ -74,9 +96,13 @@ class KeyframeStore:
     pixel rays (geometry.py:37-42, what solve_GN_calib computes per call, global_opt.py:172).
     They are kept current by ``append`` / ``set_keyframe`` / ``refresh``; code that writes
     X / C / n_obs directly calls ``refresh(k)`` (the reference-compatible FactorGraph reads
-    only X / C / n_obs / T_WC and needs nothing)."""
+    only X / C / n_obs / T_WC and needs nothing).
 
-    def __init__(self, capacity, h, w, device="cuda", K=None):
+    ``keep_rgb=True`` also keeps what the map export and save_traj read (evaluate.py:23-106):
+    ``rgb`` [cap,HW,3] u8, the keyframe image as save_reconstruction quantises it, and
+    ``frame_ids``, a host list of each keyframe's frame id."""
+
+    def __init__(self, capacity, h, w, device="cuda", K=None, keep_rgb=False):
         hw = h * w
         self.h, self.w = h, w
         self.X = torch.zeros((capacity, hw, 3), device=device)
@@ -89,6 +115,8 @@ class KeyframeStore:
         self.K = K
         self.X_ray = torch.zeros((capacity, hw, 3), device=device) if K is not None else None
         self.img_placeholder = torch.zeros((3, h, w), device="cpu")
+        self.rgb = torch.zeros((capacity, hw, 3), dtype=torch.uint8, device=device) if keep_rgb else None
+        self.frame_ids = [None] * capacity if keep_rgb else None
         self.size = 0
 
     def refresh(self, k):
@@ -97,7 +125,14 @@ class KeyframeStore:
         if self.X_ray is not None:
             self.X_ray[k] = constrain_points_to_ray((self.h, self.w), self.X[k:k + 1], self.K)[0]
 
-    def set_keyframe(self, k, X=None, C=None, T_WC=None, n_obs=None):
+    def set_keyframe(self, k, X=None, C=None, T_WC=None, n_obs=None, uimg=None, frame_id=None):
+        if uimg is not None or frame_id is not None:
+            if self.rgb is None:
+                raise RuntimeError("KeyframeStore: uimg / frame_id need keep_rgb=True")
+            if uimg is not None:
+                self.rgb[k] = quantize_uimg(uimg.to(self.rgb.device)).reshape(-1, 3)
+            if frame_id is not None:
+                self.frame_ids[k] = int(frame_id)
         if X is not None:
             self.X[k] = X
         if C is not None:
@@ -108,10 +143,10 @@ class KeyframeStore:
             self.n_obs[k] = n_obs
         self.refresh(k)
 
-    def append(self, X, C, T_WC, n_obs=None):
+    def append(self, X, C, T_WC, n_obs=None, uimg=None, frame_id=None):
         k = self.size
         self.size += 1
-        self.set_keyframe(k, X, C, T_WC, n_obs)
+        self.set_keyframe(k, X, C, T_WC, n_obs, uimg, frame_id)
         return k
 
     def __len__(self):

@@ -16,6 +16,7 @@ import atexit
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 __all__ = [
@@ -29,6 +30,10 @@ __all__ = [
     "CholeskyError",
     "pointmap_update",
     "edge_confidence",
+    "reconstruct",
+    "ReconPass",
+    "RECON_DTYPE",
+    "recon_tile_points",
     "RetrievalHandle",
     "retrieval_create",
     "retrieval_destroy",
@@ -675,6 +680,116 @@ def pointmap_update(mode, X, C, X_new, C_new, T=None):
                                      _ptr(C), HW, _stream(dev))
     _raise(rc, "pointmap_update")
     return X, C
+
+
+# ---------------------------------------------------------------------------------
+# map export (extension: evaluate.py:47-106 builds the cloud on the host in the reference)
+# ---------------------------------------------------------------------------------
+
+
+class ReconArgs(ctypes.Structure):
+    _fields_ = [
+        ("X", _vp), ("C", _vp), ("n_obs", _vp), ("T_WC", _vp), ("rgb", _vp), ("K", _vp),
+        ("N", _c_int64), ("HW", _c_int64), ("height", _i), ("width", _i),
+        ("thresh", _f), ("ws", _vp), ("ws_bytes", ctypes.c_size_t), ("stream", _vp),
+    ]
+
+
+lib.m3s_recon_workspace_bytes.argtypes = [_c_int64, _c_int64]
+lib.m3s_recon_workspace_bytes.restype = ctypes.c_size_t
+lib.m3s_recon_tile_points.argtypes = []
+lib.m3s_recon_tile_points.restype = _c_int64
+lib.m3s_recon_count.argtypes = [ctypes.POINTER(ReconArgs), _vp, _vp]
+lib.m3s_recon_emit.argtypes = [ctypes.POINTER(ReconArgs), _vp, _c_int64]
+
+RECON_RECORD_BYTES = 15
+# one record of the exported cloud = one vertex of the binary little-endian PLY body
+RECON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
+                        ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+
+
+def recon_tile_points() -> int:
+    """Points per tile of the map-export kernels (a tile never spans two keyframes)."""
+    return int(lib.m3s_recon_tile_points())
+
+
+class ReconPass:
+    """One count (+ emits) of the map export over N keyframes (include/m3s_backend.h, "map
+    export").  X [N,HW,3], C [N,HW] or [N,HW,1], n_obs [N], T_WC [N,8] or [N,1,8] f32; rgb
+    [N,HW,3] u8 or None (records get 0,0,0); K [3,3] f32 with img_size=(h, w), h*w == HW, or None.
+    ``count()`` returns device tensors and does not synchronise; ``emit(out, capacity)`` writes
+    min(total, capacity) records into the uint8 tensor ``out``."""
+
+    def __init__(self, X, C, n_obs, T_WC, rgb=None, K=None, img_size=None, thresh=1.5):
+        _check(X, "X", torch.float32, 3)
+        N, HW = int(X.shape[0]), int(X.shape[1])
+        if C.dim() == 3 and C.shape[-1] == 1:  # the store's [N,HW,1]
+            C = C.squeeze(-1)
+        if T_WC.dim() == 3 and T_WC.shape[1] == 1:  # the store's [N,1,8]
+            T_WC = T_WC.squeeze(1)
+        _check(C, "C", torch.float32, 2)
+        _check(n_obs, "n_obs", torch.float32, 1)
+        _check(T_WC, "T_WC", torch.float32, 2)
+        if (X.shape[2] != 3 or tuple(C.shape) != (N, HW) or n_obs.shape[0] != N
+                or tuple(T_WC.shape) != (N, 8)):
+            raise RuntimeError("reconstruct: expected X [N,HW,3], C [N,HW], n_obs [N], T_WC [N,8]")
+        if rgb is not None:
+            _check(rgb, "rgb", torch.uint8, 3)
+            if tuple(rgb.shape) != (N, HW, 3):
+                raise RuntimeError("reconstruct: expected rgb [N,HW,3]")
+        h = w = 0
+        if K is not None:
+            _check(K, "K", torch.float32, 2)
+            if tuple(K.shape) != (3, 3):
+                raise RuntimeError("reconstruct: expected K [3,3]")
+            if img_size is None:
+                raise RuntimeError("reconstruct: img_size=(height, width) is required with K")
+            h, w = int(img_size[0]), int(img_size[1])
+            if h * w != HW:
+                raise RuntimeError(f"reconstruct: img_size {h}x{w} does not match HW={HW}")
+        dev = _on_device(X=X, C=C, n_obs=n_obs, T_WC=T_WC, rgb=rgb, K=K)
+        self.device, self.N, self.HW = dev, N, HW
+        self._keep = (X, C, n_obs, T_WC, rgb, K)  # the args struct borrows their storage
+        nbytes = int(lib.m3s_recon_workspace_bytes(N, HW))
+        self._ws = torch.empty((nbytes // 8 + 1,), dtype=torch.int64, device=dev)
+        self._args = ReconArgs(_ptr(X), _ptr(C), _ptr(n_obs), _ptr(T_WC), _ptr(rgb), _ptr(K), N, HW,
+                               h, w, float(thresh), _ptr(self._ws), self._ws.numel() * 8, None)
+
+    def count(self):
+        counts = torch.empty((self.N,), dtype=torch.int64, device=self.device)
+        total = torch.empty((1,), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._args.stream = _stream(self.device)
+            rc = lib.m3s_recon_count(ctypes.byref(self._args), _ptr(counts), _ptr(total))
+        _raise(rc, "recon_count")
+        return counts, total
+
+    def emit(self, out, capacity):
+        _check(out, "out", torch.uint8, 1)
+        capacity = int(capacity)
+        if capacity < 0 or out.numel() < RECON_RECORD_BYTES * capacity:
+            raise RuntimeError("recon_emit: out holds fewer than 15 * capacity bytes")
+        if out.device != self.device:
+            raise RuntimeError(f"out must be on {self.device}, got {out.device}")
+        with torch.cuda.device(self.device):
+            self._args.stream = _stream(self.device)
+            rc = lib.m3s_recon_emit(ctypes.byref(self._args), _ptr(out), capacity)
+        _raise(rc, "recon_emit")
+        return out
+
+
+def reconstruct(X, C, n_obs, T_WC, rgb=None, K=None, img_size=None, thresh=1.5):
+    """The keyframes' points with C / n_obs > thresh, transformed to the world by T_WC (on their
+    pixel rays through K when K is given), with their colours, in (keyframe, pixel) order.
+    Returns (body, counts): body uint8 [15 * total] on the device -- the vertex records of a
+    binary little-endian PLY, ``body.cpu().numpy().view(RECON_DTYPE)`` -- and counts [N] i64, the
+    kept points per keyframe.  One host synchronisation (to size ``body``)."""
+    p = ReconPass(X, C, n_obs, T_WC, rgb, K, img_size, thresh)
+    counts, total = p.count()
+    n = int(total.item())
+    body = torch.empty((RECON_RECORD_BYTES * n,), dtype=torch.uint8, device=p.device)
+    p.emit(body, n)
+    return body, counts
 
 # ---------------------------------------------------------------------------------
 # loop-closure retrieval (extension: retrieval_database.py:43-166 runs in torch / numpy / Cython)
