@@ -433,6 +433,58 @@ int m3s_recon_count(const m3s_recon_args* args, int64_t* counts /* [N] dev */,
                     int64_t* total /* [1] dev */);
 int m3s_recon_emit(const m3s_recon_args* args, void* out /* dev, 15*capacity B */, int64_t capacity);
 
+/* ---------------- head finish: raw MASt3R head outputs -> X, C, D, Q ---------------- */
+
+/*
+ * One streaming pass from the raw tensors of a MASt3R head to the X, C, D, Q that matching, the
+ * tracker and the edge construction consume.  Replaces the torch chain of
+ * Cat_MLP_LocalFeatures_DPT_Pts3d.forward after the two sub-heads (catmlp_dpt_head.py:83-95:
+ * transpose, view, pixel_shuffle, cat, postprocess), reg_dense_depth / reg_dense_conf
+ * (dust3r/heads/postprocess.py:22-58), reg_desc (catmlp_dpt_head.py:17-22) and downsample
+ * (mast3r_utils.py:43-52).  Extension op.  All tensors f32 on the device; batch strides in elements
+ * (a [:, :4] view of a larger tensor is accepted), every other dimension contiguous.
+ *   pts   [B,4,H,W] channel-planar: the DPT output (x, y, z, confidence logit)
+ *   feat  NULL (no descriptor work: D and Q must be NULL too), or
+ *         TOKENS [B,S,(F+1) p^2], S = (H/p)(W/p), p = patch = 16: the MLP output before the
+ *                transpose and pixel_shuffle; pixel (v,u), channel c is at token (v/p)(W/p) + u/p,
+ *                offset c p^2 + (v%p) p + (u%p); needs H % p == 0 and W % p == 0
+ *         PLANAR [B,F+1,H,W]: channels 4.. of the head's raw output (any H, W)
+ *         channels 0..F-1 the descriptor, channel F the descriptor-confidence logit; 1 <= F <= 32
+ *   outputs, h = ceil(H/ds), w = ceil(W/ds), pixel (v ds, u ds) of the input (Python's [::ds]):
+ *         X [B,h,w,3], C [B,h,w], D [B,h,w,F], Q [B,h,w], contiguous
+ * f32 arithmetic, uncontracted, correctly rounded sqrt and divide, in this order:
+ *   s = (x x + y y) + z z;  d = sqrt(s);  m = d < 1e-8f ? 1e-8f : d   (a NaN d stays NaN)
+ *   X_c = (x_c / m) expm1f(d)
+ *   C   = conf_vmin + min'(expf(a), conf_vmax - conf_vmin)            (min' keeps a NaN, as clip)
+ *   n   = sqrt(((f_0 f_0 + f_1 f_1) + f_2 f_2) + ... + f_{F-1} f_{F-1});  D_c = f_c / n  (n = 0: NaN)
+ *   Q   = dconf_vmin + min'(expf(q), dconf_vmax - dconf_vmin)
+ * so D is a function of the inputs alone, bit for bit; X, C, Q carry the device library's expm1f /
+ * expf.  Only the checkpoint's modes exist (depth exp unbounded, conf exp, desc norm, two
+ * confidences): the mode fields must be 0.  Enqueues on `stream`, never synchronises, uses no
+ * workspace; two runs give the same bytes.  B H W == 0: M3S_OK.
+ */
+enum { M3S_HEAD_TOKENS = 0, M3S_HEAD_PLANAR = 1 };
+enum { M3S_HEAD_DEPTH_EXP = 0, M3S_HEAD_DEPTH_LINEAR = 1, M3S_HEAD_DEPTH_SQUARE = 2 };
+enum { M3S_HEAD_CONF_EXP = 0, M3S_HEAD_CONF_SIGMOID = 1 };
+enum { M3S_HEAD_DESC_NORM = 0 };
+typedef struct m3s_head_args {
+  const float* pts;
+  const float* feat;   /* or NULL */
+  int64_t pts_bstride, feat_bstride; /* elements between batch items */
+  int64_t B, H, W, F;
+  int layout;          /* M3S_HEAD_TOKENS / M3S_HEAD_PLANAR */
+  int patch;           /* 16 */
+  int downsample;      /* ds >= 1 */
+  int depth_mode, conf_mode, desc_mode, single_conf; /* all 0: the checkpoint's */
+  float conf_vmin, conf_vmax, dconf_vmin, dconf_vmax;
+  float* X;
+  float* C;
+  float* D;            /* D and Q: both given or both NULL */
+  float* Q;
+  void* stream;
+} m3s_head_args;
+int m3s_head_finish(const m3s_head_args* args);
+
 /* ---------------- loop-closure retrieval (ASMK) ---------------- */
 
 /*

@@ -1,7 +1,7 @@
 """Hot-path parameters of the reference configuration (values only).
 
-Source: /root/reference/config/base.yaml:8-14 (matching), :16-33 (tracking), :35-50 (local_opt),
-:52-58 (retrieval, reloc);
+Source: /root/reference/config/base.yaml:3-5 (dataset.img_downsample), :8-14 (matching),
+:16-33 (tracking), :35-50 (local_opt), :52-58 (retrieval, reloc);
 calib.yaml:1-6 switches ``use_calib`` on.  ``load_config`` reads the reference's YAML
 format (``inherit:`` chaining, floats like ``1e-8``) with a SafeLoader, like
 mast3r_slam/config.py:7-48.
@@ -15,6 +15,9 @@ import yaml
 
 DEFAULT_CONFIG = {
     "use_calib": False,
+    "dataset": {  # base.yaml:3-5 (the key m3s.mast3r_utils reads)
+        "img_downsample": 1,
+    },
     "matching": {
         "max_iter": 10,
         "lambda_init": 1e-8,

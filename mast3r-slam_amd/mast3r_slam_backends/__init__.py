@@ -34,6 +34,7 @@ __all__ = [
     "ReconPass",
     "RECON_DTYPE",
     "recon_tile_points",
+    "head_finish",
     "RetrievalHandle",
     "retrieval_create",
     "retrieval_destroy",
@@ -790,6 +791,118 @@ def reconstruct(X, C, n_obs, T_WC, rgb=None, K=None, img_size=None, thresh=1.5):
     body = torch.empty((RECON_RECORD_BYTES * n,), dtype=torch.uint8, device=p.device)
     p.emit(body, n)
     return body, counts
+
+# ---------------------------------------------------------------------------------
+# head finish (extension: catmlp_dpt_head.py:83-95, postprocess.py:22-58 and
+# mast3r_utils.py:43-52 run as a chain of torch kernels in the reference)
+# ---------------------------------------------------------------------------------
+
+
+class HeadArgs(ctypes.Structure):
+    """Mirror of ``m3s_head_args`` (include/m3s_backend.h)."""
+
+    _fields_ = [
+        ("pts", _vp), ("feat", _vp), ("pts_bstride", _c_int64), ("feat_bstride", _c_int64),
+        ("B", _c_int64), ("H", _c_int64), ("W", _c_int64), ("F", _c_int64),
+        ("layout", _i), ("patch", _i), ("downsample", _i),
+        ("depth_mode", _i), ("conf_mode", _i), ("desc_mode", _i), ("single_conf", _i),
+        ("conf_vmin", _f), ("conf_vmax", _f), ("dconf_vmin", _f), ("dconf_vmax", _f),
+        ("X", _vp), ("C", _vp), ("D", _vp), ("Q", _vp), ("stream", _vp),
+    ]
+
+
+lib.m3s_head_finish.argtypes = [ctypes.POINTER(HeadArgs)]
+
+HEAD_LAYOUTS = {"tokens": 0, "planar": 1}
+HEAD_MAX_F = 32
+
+
+def _check_batched(t, name, ndim):
+    """f32, ``ndim`` dims, every dimension but the batch contiguous (a ``[:, :4]`` view passes)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"expected scalar type Float but found {_DT_NAME.get(t.dtype, t.dtype)} ({name})")
+    if t.dim() != ndim:
+        raise RuntimeError(f"head_finish: {name} must have {ndim} dims, got {t.dim()}")
+    if t.numel() and not t[0].is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous inside a batch item")
+    if t.shape[0] > 1 and t.numel() and t.stride(0) < t[0].numel():
+        raise RuntimeError(f"{name}: batch items overlap")
+
+
+def head_finish(pts, feat, *, layout="tokens", patch=16, downsample=1, conf=(1.0, float("inf")),
+                desc_conf=(0.0, float("inf")), out=None):
+    """Raw MASt3R head outputs -> (X [B,h,w,3], C [B,h,w], D [B,h,w,F], Q [B,h,w]) in one launch
+    (include/m3s_backend.h, "head finish").  ``pts`` [B,4,H,W] is the DPT output; ``feat`` is the
+    local-feature MLP's output [B,S,(F+1)*patch^2] (``layout="tokens"``) or the pixel-shuffled
+    [B,F+1,H,W] (``"planar"``), or None: then (X, C, None, None) and no descriptor work.  Batch
+    items may be strided (``raw[:, :4]``).  h, w = ceil(H / downsample), ceil(W / downsample): the
+    ``[::downsample]`` pixels.  ``conf`` / ``desc_conf`` are the (vmin, vmax) of the exp modes.
+    ``out=(X, C, D, Q)``: caller-owned contiguous tensors, e.g. slot k of a stacked buffer."""
+    if layout not in HEAD_LAYOUTS:
+        raise RuntimeError(f"head_finish: unknown layout {layout!r} (expected one of {sorted(HEAD_LAYOUTS)})")
+    patch, ds = int(patch), int(downsample)
+    if patch != 16:
+        raise RuntimeError(f"head_finish: patch must be 16, got {patch}")
+    if ds < 1:
+        raise RuntimeError(f"head_finish: downsample must be >= 1, got {ds}")
+    _check_batched(pts, "pts", 4)
+    B, ch, H, W = pts.shape
+    if ch != 4:
+        raise RuntimeError(f"head_finish: pts must be [B,4,H,W], got {tuple(pts.shape)}")
+    F = 0
+    if feat is not None:
+        if layout == "tokens":
+            _check_batched(feat, "feat", 3)
+            if H % patch or W % patch:
+                raise RuntimeError(f"head_finish: the tokens layout needs H and W to be multiples of "
+                                   f"{patch}, got {H}x{W}")
+            S, pp = (H // patch) * (W // patch), patch * patch
+            if feat.shape[0] != B or feat.shape[1] != S or feat.shape[2] % pp:
+                raise RuntimeError(f"head_finish: feat must be [B,{S},(F+1)*{pp}] for pts "
+                                   f"{tuple(pts.shape)}, got {tuple(feat.shape)}")
+            F = feat.shape[2] // pp - 1
+        else:
+            _check_batched(feat, "feat", 4)
+            if feat.shape[0] != B or tuple(feat.shape[2:]) != (H, W):
+                raise RuntimeError(f"head_finish: feat must be [B,F+1,{H},{W}] for pts "
+                                   f"{tuple(pts.shape)}, got {tuple(feat.shape)}")
+            F = feat.shape[1] - 1
+        if not 1 <= F <= HEAD_MAX_F:
+            raise RuntimeError(f"head_finish: F must be in 1..{HEAD_MAX_F}, got {F}")
+    h, w = -(-H // ds), -(-W // ds)
+    shapes = ((B, h, w, 3), (B, h, w), (B, h, w, F), (B, h, w))
+    names = ("X", "C", "D", "Q")
+    if out is None:
+        dev0 = pts.device
+        out = tuple(torch.empty(s, dtype=torch.float32, device=dev0) if feat is not None or k < 2
+                    else None for k, s in enumerate(shapes))
+    else:
+        out = tuple(out)
+        if len(out) != 4:
+            raise RuntimeError("head_finish: out must be (X, C, D, Q)")
+        for k, (name, t, s) in enumerate(zip(names, out, shapes)):
+            if feat is None and k >= 2:
+                continue  # left untouched
+            if t is None:
+                raise RuntimeError(f"head_finish: out {name} is missing")
+            _check(t, f"out {name}", torch.float32, len(s))
+            if tuple(t.shape) != s:
+                raise RuntimeError(f"head_finish: out {name} must be {s}, got {tuple(t.shape)}")
+    X, C = out[0], out[1]
+    D, Q = (out[2], out[3]) if feat is not None else (None, None)
+    dev = _on_device(pts=pts, feat=feat, X=X, C=C, D=D, Q=Q)
+    a = HeadArgs(_ptr(pts), _ptr(feat), pts.stride(0), feat.stride(0) if feat is not None else 0,
+                 B, H, W, F, HEAD_LAYOUTS[layout], patch, min(ds, 2 ** 30), 0, 0, 0, 0,
+                 float(conf[0]), float(conf[1]), float(desc_conf[0]), float(desc_conf[1]),
+                 _ptr(X), _ptr(C), _ptr(D), _ptr(Q), None)
+    with torch.cuda.device(dev):
+        a.stream = _stream(dev)
+        rc = lib.m3s_head_finish(ctypes.byref(a))
+    _raise(rc, "head_finish")
+    return X, C, D, Q
+
 
 # ---------------------------------------------------------------------------------
 # loop-closure retrieval (extension: retrieval_database.py:43-166 runs in torch / numpy / Cython)
