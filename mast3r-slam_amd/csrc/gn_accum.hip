@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <type_traits>
 
 #include "edge_reduce.h"
 #include "gn_kernels.h"
@@ -202,8 +203,11 @@ __device__ __forceinline__ void point_body_x(const PointsIn<V>& p, V X0, V X1, V
         const V e1 = ry - n1i_inv * p.xi1;
         const V e2 = rz - n1i_inv * p.xi2;
         const V e3 = n1j - n1i;
-        const V swr = vsel(valid, vsplat(P.s0_inv, sq) * sq, zero);
-        const V swd = vsel(valid, vsplat(P.s1_inv, sq) * sq, zero);
+        // one select for both weights: (1/sigma) * 0 = +0 for a finite positive 1/sigma, the bits of
+        // selecting each product
+        const V sqv = vsel(valid, sq, zero);
+        const V swr = vsplat(P.s0_inv, sq) * sqv;
+        const V swd = vsplat(P.s1_inv, sq) * sqv;
         const V wcr = swr * swr, wcd = swd * swd;
         const V w0 = huber(swr * e0) * wcr;
         const V w1 = huber(swr * e1) * wcr;
@@ -254,8 +258,11 @@ __device__ __forceinline__ void point_body_x(const PointsIn<V>& p, V X0, V X1, V
                      vand(vand(vgt(u, P.pb_lo), vlt(u, P.pb_hi_u)), vand(vgt(v, P.pb_lo), vlt(v, P.pb_hi_v))));
         const V e0 = u - p.ut;
         const V e1 = v - p.vt;
-        const V swp = vsel(valid, vsplat(P.s0_inv, sq) * sq, zero);
-        const V swd = vsel(valid, vsplat(P.s1_inv, sq) * sq, zero);
+        // one select for both weights: (1/sigma) * 0 = +0 for a finite positive 1/sigma, the bits of
+        // selecting each product
+        const V sqv = vsel(valid, sq, zero);
+        const V swp = vsplat(P.s0_inv, sq) * sqv;
+        const V swd = vsplat(P.s1_inv, sq) * sqv;
         const V wcp = swp * swp, wcd = swd * swd;
         const V w0 = huber(swp * e0) * wcp;
         const V w1 = huber(swp * e1) * wcp;
@@ -355,14 +362,25 @@ __device__ __forceinline__ void pixel_of(int ind, const AccParams& P, float& ut,
     ut = (float)(ind - (int)q * P.width);
 }
 
-// The packed calib record's match (code & 0x7fffffff = v << 16 | u, AccParams::pack_uv): its
-// flat index v W + u (24-bit multiply-add) and its pixel as floats.
-__device__ __forceinline__ int uv_index(int code, int width) {
-    return (int)__umul24((unsigned)(code >> 16) & 0x7fffu, (unsigned)width) + (code & 0xffff);
+// The packed calib record's match (code = invalid << 31 | v << 16 | u, AccParams::pack_uv): the
+// byte offset of its flat index v W + u in a float array, and its pixel as floats.
+// code + v (W - 65536) = v W + u + (invalid << 31) in 32-bit arithmetic, and the shift by 2 drops
+// the invalid bit: a bit-field extract, one 24-bit multiply-add and a shift, with no mask of u
+// (which then only feeds its convert: a word select) -- an unsigned 32-bit offset from a uniform
+// base, not a sign-extended 64-bit address (HW <= kPackedMaxHW: launch_accum_packed).
+__device__ __forceinline__ unsigned uv_offset4(int code, int width) {
+    const int v = (code >> 16) & 0x7fff;
+    return (unsigned)(__mul24(v, width - 65536) + code) << 2;
 }
 __device__ __forceinline__ void uv_pixel(int code, float& ut, float& vt) {
     ut = (float)(code & 0xffff);
     vt = (float)((code >> 16) & 0x7fff);
+}
+// a load at an unsigned 32-bit byte offset from a (workgroup-uniform) base: the global_load form
+// with the base in SGPRs and the offset in one VGPR (element i after it: the immediate offset)
+template <typename T>
+__device__ __forceinline__ T ld_off(const void* base, unsigned byte_off, int i = 0) {
+    return reinterpret_cast<const T*>(static_cast<const char*>(base) + byte_off)[i];
 }
 // the pack's record code for match index ind (valid or not: bit 31 marks invalid)
 __device__ __forceinline__ int pack_code(int ind, bool ok, const AccParams& P) {
@@ -435,55 +453,105 @@ struct AccStage {
     const float* rc_tv = nullptr;
     unsigned rc_m = 0;             // RC: k / W by multiply-shift
     int rc_sh = 0, rc_w = 1;
+    unsigned rc_q = 0, rc_dq = 0;  // RC, fixed columns (fix_columns): the lane's pixel row, its advance per step
     int width = 1;                 // PK calib: the image width (record pixel -> flat index)
 
-    template <int M>
-    __device__ __forceinline__ void load(const float* __restrict__ Xj_b, const float* __restrict__ Xi_b,
-                                         const float* __restrict__ Zi_b, int k) {
+    // RC, when the points of a step are whole pixel rows (NP * kAccThreads a multiple of W): a lane
+    // keeps its columns from step to step and moves down `rows` rows, so its tu are loaded, and
+    // its first point k divided by W, once per chunk instead of once per step.
+    __device__ __forceinline__ void fix_columns(int k, int rows) {
+        const unsigned q = (unsigned)(((uint64_t)(unsigned)k * rc_m) >> rc_sh);
+        const unsigned u = (unsigned)k - q * (unsigned)rc_w;
+        if constexpr (NP == 4) {
+            const float4 ta = ld_off<float4>(rc_tu, u * 4u);
+            xv[4] = ta.x; xv[5] = ta.y; xv[6] = ta.z; xv[7] = ta.w;
+        } else {
+            const float2 ta = ld_off<float2>(rc_tu, u * 4u);
+            xv[2] = ta.x; xv[3] = ta.y;
+        }
+        rc_q = q;
+        rc_dq = (unsigned)rows;
+    }
+
+    // The step's loads for the NP points from point k of the keyframe on.  PK: Xj_c is the chunk's
+    // Xj (advanced to the chunk's first point) and r = k - (the chunk's first point), so every
+    // address is a uniform base plus an unsigned 32-bit byte offset (HW <= kPackedMaxHW:
+    // launch_accum_packed); the unpacked kernel passes the keyframe's Xj and r = k.
+    // FIXC: after fix_columns.
+    template <int M, bool FIXC = false>
+    __device__ __forceinline__ void load(const float* __restrict__ Xj_c, const float* __restrict__ Xi_b,
+                                         const float* __restrict__ Zi_b, unsigned r, int k) {
         if constexpr (RC) {
-            // Xj_b = the depth row of keyframe j; the ray tables follow Zs (gn_depth_kernel)
+            // Xj_c = the depth row of keyframe j; the ray tables follow Zs (gn_depth_kernel)
             // (the NP points share a row: k is a multiple of NP and W of 4)
-            const unsigned q = (unsigned)(((uint64_t)(unsigned)k * rc_m) >> rc_sh);
-            const int u = k - (int)q * rc_w;
-            if constexpr (NP == 4) {
-                const float4 za = *reinterpret_cast<const float4*>(Xj_b + k);
-                const float4 ta = *reinterpret_cast<const float4*>(rc_tu + u);
-                const float t[8] = {za.x, za.y, za.z, za.w, ta.x, ta.y, ta.z, ta.w};
-#pragma unroll
-                for (int i = 0; i < 8; i++) xv[i] = t[i];
+            unsigned q;
+            if constexpr (FIXC) {
+                q = rc_q;
+                rc_q += rc_dq;
             } else {
-                const float2 za = *reinterpret_cast<const float2*>(Xj_b + k);
-                const float2 ta = *reinterpret_cast<const float2*>(rc_tu + u);
-                xv[0] = za.x; xv[1] = za.y; xv[2] = ta.x; xv[3] = ta.y;
+                q = (unsigned)(((uint64_t)(unsigned)k * rc_m) >> rc_sh);
+                const unsigned u = (unsigned)k - q * (unsigned)rc_w;
+                if constexpr (NP == 4) {
+                    const float4 ta = ld_off<float4>(rc_tu, u * 4u);
+                    xv[4] = ta.x; xv[5] = ta.y; xv[6] = ta.z; xv[7] = ta.w;
+                } else {
+                    const float2 ta = ld_off<float2>(rc_tu, u * 4u);
+                    xv[2] = ta.x; xv[3] = ta.y;
+                }
             }
-            xv[2 * NP] = rc_tv[q];
+            if constexpr (NP == 4) {
+                const float4 za = ld_off<float4>(Xj_c, r * 4u);
+                xv[0] = za.x; xv[1] = za.y; xv[2] = za.z; xv[3] = za.w;
+            } else {
+                const float2 za = ld_off<float2>(Xj_c, r * 4u);
+                xv[0] = za.x; xv[1] = za.y;
+            }
+            xv[2 * NP] = ld_off<float>(rc_tv, q * 4u);
         } else if constexpr (NP == 4) {
-            const float4 a = *reinterpret_cast<const float4*>(Xj_b + (int64_t)k * 3);
-            const float4 b = *reinterpret_cast<const float4*>(Xj_b + (int64_t)k * 3 + 4);
-            const float4 c = *reinterpret_cast<const float4*>(Xj_b + (int64_t)k * 3 + 8);
+            float4 a, b, c;
+            if constexpr (PK) {
+                a = ld_off<float4>(Xj_c, r * 12u);
+                b = ld_off<float4>(Xj_c, r * 12u, 1);
+                c = ld_off<float4>(Xj_c, r * 12u, 2);
+            } else {
+                a = *reinterpret_cast<const float4*>(Xj_c + (int64_t)k * 3);
+                b = *reinterpret_cast<const float4*>(Xj_c + (int64_t)k * 3 + 4);
+                c = *reinterpret_cast<const float4*>(Xj_c + (int64_t)k * 3 + 8);
+            }
             const float t[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
 #pragma unroll
             for (int i = 0; i < 12; i++) xv[i] = t[i];
         } else {
-            const float2 a = *reinterpret_cast<const float2*>(Xj_b + (int64_t)k * 3);
-            const float2 b = *reinterpret_cast<const float2*>(Xj_b + (int64_t)k * 3 + 2);
-            const float2 c = *reinterpret_cast<const float2*>(Xj_b + (int64_t)k * 3 + 4);
+            float2 a, b, c;
+            if constexpr (PK) {
+                a = ld_off<float2>(Xj_c, r * 12u);
+                b = ld_off<float2>(Xj_c, r * 12u, 1);
+                c = ld_off<float2>(Xj_c, r * 12u, 2);
+            } else {
+                a = *reinterpret_cast<const float2*>(Xj_c + (int64_t)k * 3);
+                b = *reinterpret_cast<const float2*>(Xj_c + (int64_t)k * 3 + 2);
+                c = *reinterpret_cast<const float2*>(Xj_c + (int64_t)k * 3 + 4);
+            }
             const float t[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
 #pragma unroll
             for (int i = 0; i < 6; i++) xv[i] = t[i];
         }
-        int ind[NP];
-#pragma unroll
-        for (int s = 0; s < NP; s++) ind[s] = (M == GN_CALIB && PK) ? uv_index(cd[s], width) : (cd[s] & 0x7fffffff);
 #pragma unroll
         for (int s = 0; s < NP; s++) {
             if constexpr (M == GN_CALIB) {
                 if constexpr (PK)
-                    g[s][2] = Zi_b[ind[s]];
+                    g[s][2] = ld_off<float>(Zi_b, uv_offset4(cd[s], width));
                 else
-                    g[s][2] = Xi_b[(int64_t)ind[s] * 3 + 2];
+                    g[s][2] = Xi_b[(int64_t)(cd[s] & 0x7fffffff) * 3 + 2];
+            } else if constexpr (PK) {
+                // 12 (index | invalid << 31) = 12 index in 32 bits: no mask (HW <= kPackedMaxHW)
+                const float* xp =
+                    reinterpret_cast<const float*>(reinterpret_cast<const char*>(Xi_b) + (unsigned)cd[s] * 12u);
+                g[s][0] = xp[0];
+                g[s][1] = xp[1];
+                g[s][2] = xp[2];
             } else {
-                const float* xp = Xi_b + (int64_t)ind[s] * 3;
+                const float* xp = Xi_b + (int64_t)(cd[s] & 0x7fffffff) * 3;
                 g[s][0] = xp[0];
                 g[s][1] = xp[1];
                 g[s][2] = xp[2];
@@ -644,7 +712,7 @@ __global__ __launch_bounds__(kAccThreads) void gn_accum_kernel(
             }
             AccStage<MODE, false, false, NP> st;
             st.set(int4{code[0], sqb[0], code[1], sqb[1]}, int4{code[2], sqb[2], code[3], sqb[3]});
-            st.template load<MODE>(Xj_b, Xi_b, nullptr, k);  // calib: the depth from Xs ...
+            st.template load<MODE>(Xj_b, Xi_b, nullptr, (unsigned)k, k);  // calib: the depth from Xs ...
             if constexpr (MODE == GN_CALIB) {
 #pragma unroll
                 for (int s = 0; s < NP; s++)  // ... as the inverse depth gn_depth_kernel tabulates
@@ -923,9 +991,11 @@ struct RawSrc {
 
 // One lane's steps of the packed accumulate (NP points per step); the records of the next step
 // are loaded one step ahead.  RC: Xj_b is keyframe j's depth row and x, y come from the ray
-// tables that follow Zs (total = N * HW floats of depth).  FIRST (NP = 4): the records are built
+// tables that follow Zs (total = N * HW floats of depth).  FIRST: the records are built
 // from the reference's inputs exactly as gn_pack_kernel builds them (and stored for the later
 // iterations) instead of being read: the per-call pack pass is folded into the first iteration.
+// None of the loop shapes below changes a floating-point operation, an operand or the order of
+// a lane's sums: tests/test_gpu_accum_trim.py holds the results to a recording, bit for bit.
 template <int MODE, bool RC, int NP = 4, bool FIRST = false>
 __device__ __forceinline__ void accum_steps(const float* __restrict__ Xj_b, const float* __restrict__ Xi_b,
                                             const float* __restrict__ Zi_b, const int4* __restrict__ pk_b,
@@ -943,15 +1013,28 @@ __device__ __forceinline__ void accum_steps(const float* __restrict__ Xj_b, cons
         cur.rc_sh = P.div_sh;
         cur.rc_w = P.width;
     }
-    // the records of NP points: one int4 per two
-    auto records = [&](int kk, int4& a, int4& b) {
+    // Everything below addresses the chunk relative to its first point k0 (a multiple of 4): the
+    // bases advanced to k0 are workgroup-uniform (SGPRs) and a lane's point r = k - k0 an unsigned
+    // 32-bit offset, so an address costs one shift instead of a sign extension and 64-bit adds.
+    const unsigned n = k1 > k0 ? (unsigned)(k1 - k0) : 0u;
+    const float* __restrict__ Xj_c = RC ? Xj_b + k0 : Xj_b + (int64_t)k0 * 3;
+    const int4* __restrict__ pk_c = pk_b + k0 / 2;
+    const uint8_t* __restrict__ valid_c = FIRST ? raw.valid + k0 : nullptr;
+    const int64_t* __restrict__ idx_c = FIRST ? raw.idx + k0 : nullptr;
+    const float* __restrict__ Q_c = FIRST ? raw.Q + k0 : nullptr;
+    const float* __restrict__ Cj_c = FIRST ? raw.Cj_b + k0 : nullptr;
+    int4* __restrict__ pkw_c = FIRST ? raw.pk_w + k0 / 2 : nullptr;
+    auto put = [&](unsigned byte_off, int i, const int4& v) {
+        reinterpret_cast<int4*>(reinterpret_cast<char*>(pkw_c) + byte_off)[i] = v;
+    };
+    // the records of the NP points from r on: one int4 per two
+    auto records = [&](unsigned r, int4& a, int4& b) {
         if constexpr (FIRST && NP == 2) {
             // (rays / points: 2 points per step) gn_pack_kernel's record, operation for operation
-            const uchar2 vm2 = *reinterpret_cast<const uchar2*>(raw.valid + kk);
-            const longlong2 id01 = *reinterpret_cast<const longlong2*>(raw.idx + kk);
-            const float2 q2 = *reinterpret_cast<const float2*>(raw.Q + kk);
-            const float2 cj2 =
-                raw.cj_all ? make_float2(0.f, 0.f) : *reinterpret_cast<const float2*>(raw.Cj_b + kk);
+            const uchar2 vm2 = ld_off<uchar2>(valid_c, r);
+            const longlong2 id01 = ld_off<longlong2>(idx_c, r * 8u);
+            const float2 q2 = ld_off<float2>(Q_c, r * 4u);
+            const float2 cj2 = raw.cj_all ? make_float2(0.f, 0.f) : ld_off<float2>(Cj_c, r * 4u);
             const bool vm[2] = {vm2.x != 0, vm2.y != 0};
             const int64_t ids[2] = {id01.x, id01.y};
             const float qs[2] = {q2.x, q2.y};
@@ -966,14 +1049,13 @@ __device__ __forceinline__ void accum_steps(const float* __restrict__ Xj_b, cons
                 sqb[s] = __float_as_int(sqrt_cr(qs[s]));
             }
             a = int4{code[0], sqb[0], code[1], sqb[1]};
-            raw.pk_w[kk / 2] = a;
+            put(r * 8u, 0, a);
         } else if constexpr (FIRST) {
-            const uchar4 vm4 = *reinterpret_cast<const uchar4*>(raw.valid + kk);
-            const longlong2 id01 = *reinterpret_cast<const longlong2*>(raw.idx + kk);
-            const longlong2 id23 = *reinterpret_cast<const longlong2*>(raw.idx + kk + 2);
-            const float4 q4 = *reinterpret_cast<const float4*>(raw.Q + kk);
-            const float4 cj4 =
-                raw.cj_all ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(raw.Cj_b + kk);
+            const uchar4 vm4 = ld_off<uchar4>(valid_c, r);
+            const longlong2 id01 = ld_off<longlong2>(idx_c, r * 8u);
+            const longlong2 id23 = ld_off<longlong2>(idx_c, r * 8u, 1);
+            const float4 q4 = ld_off<float4>(Q_c, r * 4u);
+            const float4 cj4 = raw.cj_all ? make_float4(0.f, 0.f, 0.f, 0.f) : ld_off<float4>(Cj_c, r * 4u);
             const bool vm[4] = {vm4.x != 0, vm4.y != 0, vm4.z != 0, vm4.w != 0};
             const int64_t ids[4] = {id01.x, id01.y, id23.x, id23.y};
             const float qs[4] = {q4.x, q4.y, q4.z, q4.w};
@@ -989,46 +1071,90 @@ __device__ __forceinline__ void accum_steps(const float* __restrict__ Xj_b, cons
             }
             a = int4{code[0], sqb[0], code[1], sqb[1]};
             b = int4{code[2], sqb[2], code[3], sqb[3]};
-            raw.pk_w[kk / 2] = a;
-            raw.pk_w[kk / 2 + 1] = b;
+            put(r * 8u, 0, a);
+            put(r * 8u, 1, b);
         } else {
-            a = pk_b[kk / 2];
-            if constexpr (NP == 4) b = pk_b[kk / 2 + 1];
+            a = ld_off<int4>(pk_c, r * 8u);
+            if constexpr (NP == 4) b = ld_off<int4>(pk_c, r * 8u, 1);
         }
     };
-    int4 na = int4{0, 0, 0, 0}, nb = int4{0, 0, 0, 0};
-    int k = k0 + NP * threadIdx.x;
-    if (k < k1) records(k, na, nb);
-    for (; k < k1; k += S) {
-#if M3S_ACC_DIAG == 1
-        // diagnostics: compute only (the first step's data, re-used: no memory after it)
-        if (k == k0 + NP * (int)threadIdx.x) {
-            cur.set(na, nb);
-            cur.template load<MODE>(Xj_b, Xi_b, Zi_b, k);
+    // FIXC: the steps are whole pixel rows, a lane keeps its columns (AccStage::fix_columns)
+    auto steps = [&](auto fixc_tag) {
+        constexpr bool FIXC = decltype(fixc_tag)::value;
+        int4 na = int4{0, 0, 0, 0}, nb = int4{0, 0, 0, 0};
+        unsigned r = NP * threadIdx.x;
+        if (r < n) {
+            records(r, na, nb);
+            if constexpr (FIXC) cur.fix_columns(k0 + (int)r, S / P.width);
         }
-        cur.template compute<MODE>(T, P, acc);
-        __builtin_amdgcn_sched_barrier(0);
-        continue;
-#elif M3S_ACC_DIAG == 2
-        // diagnostics: memory only -- the first step computed (so the system stays solvable and
-        // the iterations keep running), then every step's loads with each value merely consumed
-        cur.set(na, nb);
-        if (k + S < k1) records(k + S, na, nb);
-        cur.template load<MODE>(Xj_b, Xi_b, Zi_b, k);
-        if (k == k0 + NP * (int)threadIdx.x) {
+#if M3S_ACC_DIAG == 0
+        // The step loop unrolled by two over two record sets used alternately: while one set is
+        // computed on, the other receives the next step's records, so no set is copied into
+        // another (a rotating pair cost 16 v_mov per step).  An odd step count leaves after the
+        // first half; a lane outside the last, partial step (r >= n) leaves before it.
+        auto step = [&](const int4& a, const int4& b, unsigned rr) {
+            cur.set(a, b);
+            cur.template load<MODE, FIXC>(Xj_c, Xi_b, Zi_b, rr, k0 + (int)rr);
             cur.template compute<MODE>(T, P, acc);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 3 * NP; q++) asm volatile("" ::"v"(cur.xv[q]));
-#pragma unroll
-            for (int q = 0; q < NP; q++) asm volatile("" ::"v"(cur.g[q][2]), "v"(cur.g[q][0]), "v"(cur.cd[q]), "v"(cur.sb[q]));
+        };
+        int4 ma = int4{0, 0, 0, 0}, mb = int4{0, 0, 0, 0};
+        if constexpr (FIRST && NP == 4) {
+            // The records are built, not prefetched: building a step's records needs its inputs
+            // at once, so building them a step ahead hid no latency and only kept a second set
+            // live through the point math (calib: 101 VGPRs, 4 waves per SIMD; 95 and 5 this
+            // way).  Each step builds its own: the same builds, stores and sums in the same order
+            // per lane.  (At 2 points per step this form needs MORE registers: rays 95 against 82.)
+            while (r < n) {
+                step(na, nb, r);
+                r += S;
+                if (r < n) records(r, na, nb);
+            }
+        } else
+        while (r < n) {
+            if (r + S < n) records(r + S, ma, mb);
+            step(na, nb, r);
+            r += S;
+            if (r >= n) break;
+            if (r + S < n) records(r + S, na, nb);
+            step(ma, mb, r);
+            r += S;
         }
-        continue;
+#else
+        const unsigned r0 = r;
+        for (; r < n; r += S) {
+#if M3S_ACC_DIAG == 1
+            // diagnostics: compute only (the first step's data, re-used: no memory after it)
+            if (r == r0) {
+                cur.set(na, nb);
+                cur.template load<MODE, FIXC>(Xj_c, Xi_b, Zi_b, r, k0 + (int)r);
+            }
+            cur.template compute<MODE>(T, P, acc);
+            __builtin_amdgcn_sched_barrier(0);
+#else
+            // diagnostics: memory only -- the first step computed (so the system stays solvable and
+            // the iterations keep running), then every step's loads with each value merely consumed
+            cur.set(na, nb);
+            if (r + S < n) records(r + S, na, nb);
+            cur.template load<MODE, FIXC>(Xj_c, Xi_b, Zi_b, r, k0 + (int)r);
+            if (r == r0) {
+                cur.template compute<MODE>(T, P, acc);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 3 * NP; q++) asm volatile("" ::"v"(cur.xv[q]));
+#pragma unroll
+                for (int q = 0; q < NP; q++) asm volatile("" ::"v"(cur.g[q][2]), "v"(cur.g[q][0]), "v"(cur.cd[q]), "v"(cur.sb[q]));
+            }
 #endif
-        cur.set(na, nb);
-        if (k + S < k1) records(k + S, na, nb);
-        cur.template load<MODE>(Xj_b, Xi_b, Zi_b, k);
-        cur.template compute<MODE>(T, P, acc);
+        }
+#endif
+    };
+    if constexpr (RC) {
+        if (S % P.width == 0)  // (workgroup-uniform; cfg3: 1024 points per step, W = 512)
+            steps(std::true_type{});
+        else
+            steps(std::false_type{});
+    } else {
+        steps(std::false_type{});
     }
 }
 
@@ -1189,6 +1315,9 @@ hipError_t launch_accum_packed(int mode, dim3 grid, hipStream_t st, const float*
                                const int4* sched, float* partials, const int* flags, const float* px,
                                const int* pcnt, int* ecnt, double* edgeblk, const EdgeSrc* first_es,
                                const float* Cs, const int* cok) {
+    // the packed kernels address an image with unsigned 32-bit byte offsets (up to 16 B per point);
+    // the driver sends larger images down the unpacked path
+    if (P.HW > kPackedMaxHW) return hipErrorInvalidValue;
     if (first_es != nullptr) {  // the first iteration builds the records (positional stream)
         if (px != nullptr) return hipErrorInvalidValue;
         const FirstSrc fs{*first_es, Cs, cok, const_cast<int4*>(pack)};

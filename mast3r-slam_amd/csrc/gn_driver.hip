@@ -100,7 +100,8 @@ int setup(const m3s_gn_args& a, Ctx& c, bool early_pack) {
             al16(a.Q) && (!two || (al16(a.idx_b) && al16(a.valid_b) && al16(a.Q_b)));
     // M3S_GN_PACK: 0 never, 1 (default) when the call runs >= 3 iterations, 2 always
     const int pack_mode = env_int("M3S_GN_PACK", 1);
-    c.packed = c.vec && a.E_local > 0 && (pack_mode == 2 || (pack_mode == 1 && a.max_iter >= 3));
+    c.packed = c.vec && a.E_local > 0 && (pack_mode == 2 || (pack_mode == 1 && a.max_iter >= 3)) &&
+               a.HW <= kPackedMaxHW;  // (32-bit byte offsets within an image: gn_accum.hip)
     // M3S_GN_COMPACT=1: the packed stream holds only the live points (gn_accum.hip).  Off by
     // default: on the bench graphs 80-90 % of the points are live, the accumulate gains 3 %
     // (cfg3) / 13 % (cfg4), and the compacting pack (Xj copies, finiteness gathers) costs more

@@ -17,6 +17,9 @@ constexpr int kNacc = 35;      // 28 (sym 7x7) + 7 (gradient)
 constexpr int kNaccPad = 36;   // partial record stride (floats)
 constexpr int kEdgeBlk = 36;   // per-edge record (doubles): Hjj packed 28 + vj 7 + pad
 constexpr int kCholTile = 64;  // dense Cholesky tile
+// largest image (points) the packed accumulate takes: it addresses an image's streams (up to 16 B
+// per point) with unsigned 32-bit byte offsets; larger images use the unpacked path
+constexpr int64_t kPackedMaxHW = int64_t(1) << 28;
 
 constexpr int kFlagDone = 0;   // set once ||dx|| < delta_thresh (skips later iterations)
 constexpr int kFlagFail = 1;   // set by the factorisation when a pivot <= 0

@@ -7,7 +7,13 @@ backward branch and its target) and counts its instructions by class.  Dividing 
 loop body processes (the accumulate: NP points per lane and step, acc_np<MODE> in gn_accum.hip)
 gives instructions per point-edge.
 
-    python tools/isa_hist.py mast3r-slam_amd/build/gn_accum.o ILi2ELb0ELb1ELb0E 4
+    python tools/isa_hist.py mast3r-slam_amd/build/gn_accum.o ILi2ELb0ELb1ELb0E 8 2
+
+The third argument is the number of points one trip through the loop processes: the packed
+accumulate's step loop is unrolled by two, so 2 x NP (calib 8, rays / points 4).  A kernel with one
+loop per path (the calib kernel: positional stream, ray-constrained stream, ray-constrained with a
+lane's columns fixed) lists its innermost loops in code order on stderr; the optional fourth
+argument picks one by that number (default: the longest).
 """
 import collections
 import json
@@ -112,11 +118,24 @@ def main():
             loops.append((k - lo + 1, lo, k))
     if not loops:
         raise SystemExit("no loop found")
+    # several latches of ONE loop: a back edge whose span lies inside another's, covers a large
+    # part of it and ends within a few instructions of its end is not an inner loop but a second
+    # latch of the same loop -- one that re-enters below the header past a skipped prefetch, or,
+    # in a loop unrolled by two that is entered at its second half, the latch of that half (the
+    # spans are code-layout spans, not natural loops).  Keep the enclosing span only.
+    loops = [(n, lo, hi) for n, lo, hi in loops
+             if not any(lo2 <= lo and hi <= hi2 and (lo2, hi2) != (lo, hi) and n >= 0.4 * n2 and hi2 - hi <= 16
+                        for n2, lo2, hi2 in loops)]
     # the hot loop: the longest INNERMOST loop (one that contains no other loop's back edge; the
     # outer task loop, which also holds the workgroup reduction, is excluded that way)
     inner = [(n, lo, hi) for n, lo, hi in loops
              if not any(lo <= lo2 and hi2 <= hi and (lo2, hi2) != (lo, hi) and hi2 < hi for _, lo2, hi2 in loops)]
-    n, lo, hi = max(inner or loops)
+    cands = sorted(inner or loops, key=lambda x: x[1])
+    for i, (n_, lo_, hi_) in enumerate(cands):  # orientation: the innermost loops in code order
+        loads = sum(1 for _, t in ins[lo_:hi_ + 1] if re.match(r"(global|buffer|flat)_load", t))
+        print(f"loop {i}: +0x{addrs[lo_] - base:x}, {n_} instructions, {loads} vector loads", file=sys.stderr)
+    # the 4th argument picks a loop by that number (a kernel with one loop per path); default: the longest
+    n, lo, hi = cands[int(sys.argv[4])] if len(sys.argv) > 4 else max(cands)
     body = [t.split()[0] for _, t in ins[lo:hi + 1]]
     hist = collections.Counter(classify(op) for op in body)
     valu = sum(v for k, v in hist.items() if k.startswith("valu"))
