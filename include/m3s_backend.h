@@ -355,6 +355,13 @@ typedef struct m3s_track_args {
 } m3s_track_args;
 
 size_t m3s_track_workspace_bytes(int64_t HW);
+/* Where m3s_track_sim3 keeps its per-workgroup partial sums inside the workspace (host only, no
+ * device call): *partials_offset = byte offset of a value-major [36][*ld] f32 table of which
+ * columns 0 .. *nblk - 1 are written (one per workgroup; the padding columns are never written
+ * nor summed).  Rows: H's upper triangle row-major (28), g (7), sum of b^2 (1).  After a call the
+ * table holds the last live iteration's partials.  M3S_ERR_INVALID (nothing written) for a null pointer or an HW
+ * that m3s_track_sim3 rejects (HW < 1, HW >= 2^31). */
+int m3s_track_workspace_layout(int64_t HW, size_t* partials_offset, int* nblk, int* ld);
 int m3s_track_sim3(const m3s_track_args* args);
 /* The last m3s_track_sim3 call's result on this host thread, on the host: info4 = {iterations,
  * converged, cholesky failed, 0}, *cost (the same values as the call's device `info` / `cost`).

@@ -469,6 +469,20 @@ extern "C" size_t m3s_track_workspace_bytes(int64_t HW) {
     return align_up(sizeof(TrackState), 256) + sizeof(float) * kTrkNacc * (size_t)track_ldp(track_blocks(HW));
 }
 
+// Where m3s_track_sim3 keeps the per-workgroup partials inside its workspace: the byte offset of the
+// value-major [36][ld] f32 table, the number of workgroups (written columns) and the row stride.
+// Host only (no device call): after a call, the table holds the last live iteration's partials.
+extern "C" int m3s_track_workspace_layout(int64_t HW, size_t* partials_offset, int* nblk, int* ld) {
+    M3S_REQUIRE(partials_offset != nullptr && nblk != nullptr && ld != nullptr,
+                "track_workspace_layout: null pointer");
+    M3S_REQUIRE(HW >= 1 && HW < ((int64_t)1 << 31), "track_workspace_layout: bad point count %lld",
+                (long long)HW);
+    *partials_offset = align_up(sizeof(TrackState), 256);
+    *nblk = track_blocks(HW);
+    *ld = track_ldp(*nblk);
+    return M3S_OK;
+}
+
 extern "C" int m3s_track_sim3(const m3s_track_args* args) {
     M3S_REQUIRE(args != nullptr, "track_sim3: null args");
     const m3s_track_args& a = *args;

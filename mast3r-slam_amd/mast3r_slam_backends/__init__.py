@@ -27,6 +27,7 @@ __all__ = [
     "gauss_newton_rays",
     "gauss_newton_calib",
     "track_sim3",
+    "track_workspace_layout",
     "CholeskyError",
     "pointmap_update",
     "edge_confidence",
@@ -528,6 +529,18 @@ lib.m3s_track_sim3.argtypes = [ctypes.POINTER(TrackArgs)]
 lib.m3s_track_workspace_bytes.restype = ctypes.c_size_t
 lib.m3s_track_workspace_bytes.argtypes = [_c_int64]
 lib.m3s_track_last_result.argtypes = [_vp, _vp]
+lib.m3s_track_workspace_layout.argtypes = [_c_int64, ctypes.POINTER(ctypes.c_size_t),
+                                           ctypes.POINTER(_i), ctypes.POINTER(_i)]
+
+
+def track_workspace_layout(HW):
+    """(partials_offset, nblk, ld) of a track_sim3 workspace for HW points: the byte offset of
+    the value-major [36][ld] float32 table of per-workgroup partial sums, of which columns
+    0 .. nblk-1 are written (rows: H upper triangle row-major 28, g 7, sum of b^2 1)."""
+    off, nblk, ld = ctypes.c_size_t(), _i(), _i()
+    _raise(lib.m3s_track_workspace_layout(int(HW), ctypes.byref(off), ctypes.byref(nblk),
+                                          ctypes.byref(ld)), "track_workspace_layout")
+    return int(off.value), int(nblk.value), int(ld.value)
 
 
 class CholeskyError(RuntimeError):
@@ -537,13 +550,17 @@ class CholeskyError(RuntimeError):
 
 def track_sim3(mode, Xf, Xk, T_WCf, T_WCk, Qk, valid, sigma0, sigma1, huber_k, max_iters,
                rel_error, delta_norm, meas_k=None, valid_meas_k=None, K=None, img_size=None,
-               pixel_border=0, z_eps=0.0, check_every=4):
+               pixel_border=0, z_eps=0.0, check_every=4, ws=None):
     """Sim3 GN of one frame against its keyframe (tracker.py:173-266) on the GPU.
 
     mode "rays" (opt_pose_ray_dist_sim3) or "calib" (opt_pose_calib_sim3); Xf [HW,3] the
     gathered frame points, Xk [HW,3], Qk [HW,1], valid [HW,1] bool, T_WCf / T_WCk lietorch
     Sim3 data [1,8] (or [8]).  Returns (T_WCf [1,8], T_CkCf [1,8], iterations, cost).
-    Raises CholeskyError when the normal equations are not positive definite."""
+    Raises CholeskyError when the normal equations are not positive definite.
+
+    ws: optional caller-owned workspace, a contiguous uint8 tensor on the inputs' device of at
+    least m3s_track_workspace_bytes(HW) bytes, used instead of a fresh allocation (its contents
+    on entry do not matter; track_workspace_layout says where the partial sums are afterwards)."""
     m = GN_RAYS if mode == "rays" else GN_CALIB
     _check(Xf, "Xf", torch.float32, 2)
     _check(Qk, "Qk", torch.float32, 2)
@@ -577,7 +594,14 @@ def track_sim3(mode, Xf, Xk, T_WCf, T_WCk, Qk, valid, sigma0, sigma1, huber_k, m
     res = torch.empty((3,), dtype=torch.float64, device=dev)
     info, cost = res[:2].view(torch.int32), res[2:]
     ws_bytes = lib.m3s_track_workspace_bytes(HW)
-    ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+    if ws is None:
+        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+    else:
+        _check(ws, "ws", torch.uint8, 1)
+        if ws.device != dev:
+            raise RuntimeError("track_sim3: ws must be on the inputs' device")
+        if ws.numel() < ws_bytes:
+            raise RuntimeError(f"track_sim3: workspace too small ({ws.numel()} < {ws_bytes} bytes)")
     a = TrackArgs()
     a.mode = m
     a.Xf, a.Qk, a.valid = Xf.data_ptr(), Qk.data_ptr(), valid.data_ptr()

@@ -60,6 +60,35 @@ def test_workspace_size_query(backend):
     assert f(1, 0, 64, 2, 2) == 0  # invalid sizes
 
 
+def test_track_workspace_layout(backend):
+    """Host only: where track_sim3 keeps its partial sums, consistent with the size query."""
+    f = backend.lib.m3s_track_workspace_layout
+    size = backend.lib.m3s_track_workspace_bytes
+    for HW in (1, 7, 256, 257, 1279, 28673, 229633, 4096 * 256 + 300, 2**31 - 1):
+        off, nblk, ld = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int()
+        assert f(HW, ctypes.byref(off), ctypes.byref(nblk), ctypes.byref(ld)) == 0
+        assert nblk.value == min((HW + 255) // 256, 4096)  # one workgroup per 256 points, capped
+        assert ld.value == (nblk.value + 3) // 4 * 4       # rows padded to float4 runs
+        assert off.value > 0 and off.value % 256 == 0
+        assert size(HW) == off.value + 4 * 36 * ld.value
+        assert backend.track_workspace_layout(HW) == (off.value, nblk.value, ld.value)
+    assert backend.track_workspace_layout(1279)[1:] == (5, 8)
+    # null pointers and invalid sizes: M3S_ERR_INVALID, nothing written
+    off, nblk, ld = ctypes.c_size_t(77), ctypes.c_int(77), ctypes.c_int(77)
+    for args in ((64, None, ctypes.byref(nblk), ctypes.byref(ld)),
+                 (64, ctypes.byref(off), None, ctypes.byref(ld)),
+                 (64, ctypes.byref(off), ctypes.byref(nblk), None)):
+        assert f(*args) == 1
+        assert b"null pointer" in backend.lib.m3s_last_error()
+    for HW in (0, -5, 2**31):
+        assert f(HW, ctypes.byref(off), ctypes.byref(nblk), ctypes.byref(ld)) == 1
+        assert b"bad point count" in backend.lib.m3s_last_error()
+        with pytest.raises(RuntimeError, match="bad point count"):
+            backend.track_workspace_layout(HW)
+    assert (off.value, nblk.value, ld.value) == (77, 77, 77)
+    assert size(0) == 0
+
+
 def test_cpu_tensors_are_rejected(backend):
     with pytest.raises(RuntimeError, match="no CPU path"):
         backend.iter_proj(torch.zeros(1, 4, 4, 9), torch.zeros(1, 16, 3), torch.zeros(1, 16, 2), 10, 1e-8, 1e-6)
