@@ -122,8 +122,9 @@ int m3s_match_iterative_proj(const float* X11, const float* X21, const float* D1
 /* ---------------- Gauss-Newton ---------------- */
 
 /* Diagnostics: with env M3S_GN_DEBUG_FLAGS set (2: silently), a GN call reads back its device
- * flags at the end (one extra synchronisation); out4 = {early exit, pivot failure, packed stream,
- * ray-constrained calib accumulate (Xj read as its depth)} of the last such call. */
+ * flags at the end (one extra synchronisation); out4 = {early exit, pivot failure (in any
+ * iteration), packed stream, ray-constrained calib accumulate (Xj read as its depth)} of the last
+ * such call. */
 void m3s_gn_debug_flags(int* out4);
 /* The same call's lagged-factor PCG: out5 = {PCG solves, their CG steps in all,
  * PCG solves that fell back to the direct factorisation, 1 if the call planned PCG iterations,

@@ -378,7 +378,7 @@ int run(const m3s_gn_args& a) {
         M3S_HIP_CHECK(hipStreamSynchronize(c.st));
         // m3s_gn_debug_flags: which accumulate path the call took (bench.py prices its bytes)
         g_dbg_flags[0] = hf[kFlagDone];
-        g_dbg_flags[1] = hf[kFlagFail];
+        g_dbg_flags[1] = (hf[kFlagFail] | hf[kFlagFailed]) != 0;  // (the retraction consumed kFlagFail)
         g_dbg_flags[2] = c.packed ? 1 : 0;
         g_dbg_flags[3] = (c.packed && c.P.raycheck && hf[kFlagNotRay] == 0) ? 1 : 0;
         g_dbg_pcg[0] = hf[kFlagPcgRuns];
@@ -393,7 +393,7 @@ int run(const m3s_gn_args& a) {
         g_dbg_pcg_plan[4] = c.sp.pcg ? c.sp.pcg_nitem : 0;
         if (dbg != 2)
             fprintf(stderr, "gn flags: done %d fail %d not_ray %d timeout %d packed %d pcg runs %d steps %d fallbacks %d\n",
-                    hf[kFlagDone], hf[kFlagFail], hf[kFlagNotRay], hf[kFlagTimeout], (int)c.packed,
+                    hf[kFlagDone], g_dbg_flags[1], hf[kFlagNotRay], hf[kFlagTimeout], (int)c.packed,
                     hf[kFlagPcgRuns], hf[kFlagPcgSteps], hf[kFlagPcgFall]);
     }
     return M3S_OK;

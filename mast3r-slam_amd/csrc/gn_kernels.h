@@ -26,7 +26,9 @@ constexpr int kFlagFail = 1;   // set by the factorisation when a pivot <= 0
 constexpr int kFlagNotRay = 2; // calib: some Xs point is not its pixel's ray times its depth
 constexpr int kFlagTimeout = 3; // sticky for the call: a bounded device-side wait gave up (chol_df
                                 // ready word, round ticket); the driver returns M3S_ERR_TIMEOUT
-// (4 and 5 are reserved: unused slots)
+constexpr int kFlagFailed = 4; // diagnostics, sticky for the call: a retraction acted on kFlagFail (it
+                               // zeroes the step and clears kFlagFail for the next iteration)
+// (5 is reserved: an unused slot)
 // The lagged-factor PCG (gn_pcg.hip) of an iteration that converged has retracted the poses
 // itself; the direct solve's launches enqueued behind it (its fallback) then return at once
 // (solve_skipped).  Set or cleared by every PCG launch; never set in iterations without one.

@@ -540,6 +540,7 @@ __global__ __launch_bounds__(256) void gn_retract_kernel(float* __restrict__ Twc
         __syncthreads();
     }
     if (tid == 0) {
+        if (fail) flags[kFlagFailed] = 1;
         flags[kFlagFail] = 0;
         if ((float)sqrt(red[0]) < delta_thresh) flags[kFlagDone] = 1;
     }

@@ -907,6 +907,7 @@ __global__ __launch_bounds__(NT) void gn_solve_kernel(SolveArgs a) {
         if (tid == 0) {
             double s = 0.0;
             for (int w = 0; w < NW; w++) s += sRed[w];
+            if (fail) a.flags[kFlagFailed] = 1;
             a.flags[kFlagFail] = 0;
             if ((float)sqrt(s) < a.delta_thresh) a.flags[kFlagDone] = 1;
         }
