@@ -493,6 +493,43 @@ typedef struct m3s_head_args {
 } m3s_head_args;
 int m3s_head_finish(const m3s_head_args* args);
 
+/* ---------------- RoPE2D: the attention's rotary position embedding, in place ---------------- */
+
+/*
+ * CroCo's curope kernel (thirdparty/mast3r/dust3r/croco/models/curope/kernels.cu,
+ * rope_2d_cuda_kernel; torch fallback pos_embed.py:112-159) as one streaming pass.  tokens
+ * [B,N,H,D], f32 or f16 on the device, updated in place; B and N strides in elements, the H stride
+ * is D and the D stride 1 (a qkv[:, :, i] view of a [B,N,3,H,D] buffer is accepted).  pos [B,N,2]
+ * int64, contiguous: (y, x) of every token.  With Q = D/4 a head's D values are
+ * [u_Y (Q) | v_Y (Q) | u_X (Q) | v_X (Q)], and for axis A in {Y, X}, i in [0, Q):
+ *   theta = (float)pos[b,n,A] * inv_freq_i,   inv_freq_i = (float)(f0 / base^(i/Q))  (host, f64)
+ *   u' = u cos(theta) - v sin(theta);   v' = v cos(theta) + u sin(theta)
+ * f32 arithmetic, uncontracted, the accurate sincosf; one rounding to the token dtype.  Only the
+ * H D run of each addressed token is read or written.  D % 4 == 0, 4 <= D <= 256.  Enqueues on
+ * `stream`, never synchronises, allocates nothing; B N == 0: M3S_OK and no launch.
+ *
+ * m3s_rope2d rotates `tokens` by `pos` (the k fields are ignored).  m3s_rope2d_pair rotates q by
+ * qpos and k by kpos in ONE launch: Nq != Nk is allowed, B, H, D and the dtype are shared, qpos
+ * and kpos may be one pointer; the bytes are those of two m3s_rope2d calls.
+ */
+enum { M3S_ROPE_F32 = 0, M3S_ROPE_F16 = 1 };
+typedef struct m3s_rope_args {
+  void* tokens;          /* q */
+  const int64_t* pos;    /* qpos */
+  int64_t N;             /* Nq */
+  int64_t bstride, nstride; /* elements */
+  void* k_tokens;        /* pair only */
+  const int64_t* k_pos;
+  int64_t k_N;
+  int64_t k_bstride, k_nstride;
+  int64_t B, H, D;
+  float base, f0;
+  int dtype;             /* M3S_ROPE_F32 / M3S_ROPE_F16 */
+  void* stream;
+} m3s_rope_args;
+int m3s_rope2d(const m3s_rope_args* args);
+int m3s_rope2d_pair(const m3s_rope_args* args);
+
 /* ---------------- loop-closure retrieval (ASMK) ---------------- */
 
 /*

@@ -36,6 +36,8 @@ __all__ = [
     "RECON_DTYPE",
     "recon_tile_points",
     "head_finish",
+    "rope_2d",
+    "rope_2d_pair",
     "RetrievalHandle",
     "retrieval_create",
     "retrieval_destroy",
@@ -926,6 +928,96 @@ def head_finish(pts, feat, *, layout="tokens", patch=16, downsample=1, conf=(1.0
         rc = lib.m3s_head_finish(ctypes.byref(a))
     _raise(rc, "head_finish")
     return X, C, D, Q
+
+
+# ---------------------------------------------------------------------------------
+# RoPE2D (croco/models/curope/kernels.cu; on ROCm the reference runs the torch fallback of
+# croco/models/pos_embed.py:112-159)
+# ---------------------------------------------------------------------------------
+
+
+class RopeArgs(ctypes.Structure):
+    """Mirror of ``m3s_rope_args`` (include/m3s_backend.h)."""
+
+    _fields_ = [
+        ("tokens", _vp), ("pos", _vp), ("N", _c_int64), ("bstride", _c_int64), ("nstride", _c_int64),
+        ("k_tokens", _vp), ("k_pos", _vp), ("k_N", _c_int64), ("k_bstride", _c_int64),
+        ("k_nstride", _c_int64),
+        ("B", _c_int64), ("H", _c_int64), ("D", _c_int64),
+        ("base", _f), ("f0", _f), ("dtype", _i), ("stream", _vp),
+    ]
+
+
+lib.m3s_rope2d.argtypes = [ctypes.POINTER(RopeArgs)]
+lib.m3s_rope2d_pair.argtypes = [ctypes.POINTER(RopeArgs)]
+
+ROPE_DTYPES = {torch.float32: 0, torch.float16: 1}
+ROPE_MAX_D = 256
+
+
+def _check_rope(tokens, positions, name, pname):
+    """The reference binding's checks (curope/kernels.cu:84-94) plus the dtypes this build has."""
+    if not isinstance(tokens, torch.Tensor) or not isinstance(positions, torch.Tensor):
+        raise TypeError(f"{name} and {pname} must be torch.Tensors")
+    if tokens.dtype not in ROPE_DTYPES:
+        raise RuntimeError(f"expected scalar type Float or Half but found "
+                           f"{_DT_NAME.get(tokens.dtype, tokens.dtype)} ({name})")
+    if tokens.dim() != 4:
+        raise RuntimeError(f"{name} must be [B,N,H,D], got {tokens.dim()} dims")
+    B, N, H, D = tokens.shape
+    if D % 4:
+        raise RuntimeError(f"token dim must be multiple of 4, got {D} ({name})")
+    if not 4 <= D <= ROPE_MAX_D:
+        raise RuntimeError(f"token dim must be in 4..{ROPE_MAX_D}, got {D} ({name})")
+    if tokens.stride(3) != 1 or tokens.stride(2) != D:
+        raise RuntimeError(f"tokens are not contiguous ({name}: the H and D strides must be (D, 1), "
+                           f"got {tuple(tokens.stride()[2:])})")
+    if tokens.stride(0) < 0 or tokens.stride(1) < 0:
+        raise RuntimeError(f"tokens are not contiguous ({name}: negative stride)")
+    if positions.dtype != torch.int64:
+        raise RuntimeError(f"expected scalar type Long but found "
+                           f"{_DT_NAME.get(positions.dtype, positions.dtype)} ({pname})")
+    if not positions.is_contiguous():
+        raise RuntimeError(f"positions are not contiguous ({pname})")
+    if tuple(positions.shape) != (B, N, 2):
+        raise RuntimeError(f"bad pos.shape: {pname} must be {(B, N, 2)} for {name} "
+                           f"{tuple(tokens.shape)}, got {tuple(positions.shape)}")
+
+
+def rope_2d(tokens, positions, base, F0=1.0):
+    """RoPE2D in place, the reference extension's ``curope.rope_2d`` (include/m3s_backend.h,
+    "RoPE2D").  ``tokens`` [B,N,H,D] f32 or f16 with H, D strides (D, 1) -- contiguous, or a
+    ``qkv[:, :, i]`` view of a [B,N,3,H,D] buffer; ``positions`` [B,N,2] int64, contiguous.
+    One launch, no host synchronisation; returns None."""
+    _check_rope(tokens, positions, "tokens", "positions")
+    dev = _on_device(tokens=tokens, positions=positions)
+    B, N, H, D = tokens.shape
+    a = RopeArgs(_ptr(tokens), _ptr(positions), N, tokens.stride(0), tokens.stride(1),
+                 None, None, 0, 0, 0, B, H, D, float(base), float(F0), ROPE_DTYPES[tokens.dtype], None)
+    with torch.cuda.device(dev):
+        a.stream = _stream(dev)
+        rc = lib.m3s_rope2d(ctypes.byref(a))
+    _raise(rc, "rope_2d")
+
+
+def rope_2d_pair(q, k, qpos, kpos, base, F0=1.0):
+    """``rope_2d(q, qpos)`` and ``rope_2d(k, kpos)`` in one launch, the same bytes.  q [B,Nq,H,D]
+    and k [B,Nk,H,D] share B, H, D and the dtype; ``qpos`` and ``kpos`` may be one tensor."""
+    _check_rope(q, qpos, "q", "qpos")
+    _check_rope(k, kpos, "k", "kpos")
+    if k.dtype != q.dtype:
+        raise RuntimeError(f"rope_2d_pair: q is {q.dtype} and k is {k.dtype}")
+    if (k.shape[0], k.shape[2], k.shape[3]) != (q.shape[0], q.shape[2], q.shape[3]):
+        raise RuntimeError(f"rope_2d_pair: q {tuple(q.shape)} and k {tuple(k.shape)} must share B, H, D")
+    dev = _on_device(q=q, k=k, qpos=qpos, kpos=kpos)
+    B, Nq, H, D = q.shape
+    a = RopeArgs(_ptr(q), _ptr(qpos), Nq, q.stride(0), q.stride(1),
+                 _ptr(k), _ptr(kpos), k.shape[1], k.stride(0), k.stride(1),
+                 B, H, D, float(base), float(F0), ROPE_DTYPES[q.dtype], None)
+    with torch.cuda.device(dev):
+        a.stream = _stream(dev)
+        rc = lib.m3s_rope2d_pair(ctypes.byref(a))
+    _raise(rc, "rope_2d_pair")
 
 
 # ---------------------------------------------------------------------------------
