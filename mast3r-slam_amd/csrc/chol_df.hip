@@ -8,9 +8,8 @@
 // nt carries the RHS, so the forward substitution rides along) is a task of a single launch
 // (a plain launch, grid sized by the occupancy query; tasks claimed dynamically), processed left-looking:
 //   acc = A_ij;  for k < j: wait L_ik, L_jk final -> acc -= L_ik L_jk^T  (f64 MFMA)
-//   i == j: potrf of acc in LDS (8-column panels, per-lane 8x8 factor + row solve, MFMA rank-8
-//           trailing updates) and L_jj^-1 by doubling (8x8 blocks from the panel step, MFMA for
-//           the 16 and 32 stages) -> publish Linv_j
+//   i == j: potrf of acc and L_jj^-1 in registers, batch-cyclic over the 4 waves (potrf_bc)
+//           -> publish Linv_j
 //   i >  j: wait Linv_j -> L_ij = acc Linv_j^T (MFMA) -> publish L_ij
 // Readiness is a per-tile epoch word (ready[i * nt + j] == epoch: final in this launch).  The
 // per-XCD L2s are not coherent, so tile data crosses workgroups with agent-scope relaxed
@@ -28,21 +27,6 @@
 
 #include "gn_kernels.h"
 
-#ifndef M3S_DF_CC
-#define M3S_DF_CC 1  // 1: the register tile factor (potrf_cc: batch- or column-cyclic, M3S_DF_BC); 0: the 8-column panel steps (potrf_inverse)
-#endif
-#ifndef M3S_DF_BC
-#define M3S_DF_BC 1  // 1: batch-cyclic tile factor (potrf_bc_w); 0: 16-column blocks per wave (potrf_cc_w)
-#endif
-#ifndef M3S_DF_BC_SPEC
-#define M3S_DF_BC_SPEC 1  // potrf_bc_w: poll the counter and read the batch in one LDS round trip
-#endif
-#ifndef M3S_DF_BC_RL
-#define M3S_DF_BC_RL 1  // potrf_bc_w: the inverse's column-block products right-looking
-#endif
-#ifndef M3S_DF_BC_W
-#define M3S_DF_BC_W 4  // columns per batch of potrf_bc_w (4; 8 measured slower)
-#endif
 #ifndef M3S_DF_STAMPS
 #define M3S_DF_STAMPS 0  // diagnostics (tools/ubench_potrf64.hip): cycle stamps inside the potrf steps
 #endif
@@ -164,211 +148,20 @@ __device__ __forceinline__ double rdlane(double v, int l) {
     return __hiloint2double(hi, lo);
 }
 
-// Panel step of the tile LL^T, run by wave 0: columns c0 .. c0+7 of every row, lane = row, in
-// registers, right-looking over the 8 columns.  A pivot and the panel's diagonal-block entries
-// reach the other lanes by v_readlane (no LDS round trip, no barrier on the pivot chain), and
-// the rows below the diagonal block get their L entries in the same sweep (the panel's trsm).
-// The critical chain per column is readlane -> rsq + Newton -> scale -> the next column's
-// update in the next pivot's lane -> readlane.  Dinv[p] = 1 / l_pp (the pivot's rsqrt) for the
-// 8x8 inverse block (diag_inv8, off the chain).
-__device__ __forceinline__ void panel_factor(double* A, double* Dinv, int c0, int* flags) {
-    const int lane = threadIdx.x & 63;
-    double a[8], y[8];
-#pragma unroll
-    for (int p = 0; p < 8; p++) a[p] = A[lane * LD + c0 + p];
-    bool bad = false;
-    // lanes above a column's pivot hold upper-triangle garbage in it: never broadcast (only the
-    // lanes below a pivot are) and never stored, so no masking on the chain
-#pragma unroll
-    for (int p = 0; p < 8; p++) {
-        const double d = rdlane(a[p], c0 + p);
-        bad |= d <= 0.0;  // SimplicialLLT: fails iff a pivot <= 0 (NaN passes)
-        double r = __builtin_amdgcn_rsq(d);
-        r = r * fma(-0.5 * d * r, r, 1.5);
-        y[p] = r;
-        a[p] *= r;
-#pragma unroll
-        for (int q = p + 1; q < 8; q++) a[q] = fma(-a[p], rdlane(a[p], c0 + q), a[q]);
-    }
-    if (lane == 0) {
-        if (bad) flags[kFlagFail] = 1;
-#pragma unroll
-        for (int p = 0; p < 8; p++) Dinv[c0 + p] = y[p];
-    }
-    // every lane stores its panel row: the rows above the pivots write garbage into the tile's
-    // upper triangle, which is never read
-#pragma unroll
-    for (int p = 0; p < 8; p++) A[lane * LD + c0 + p] = a[p];
-}
-
-// the panel's 8x8 inverse block L_pp^-1 -> Li (lanes 0..7 of the calling wave: lane i solves
-// L_pp x = e_i, i.e. column i of the inverse), from L_pp in A and 1/l_pp in Dinv
-__device__ __forceinline__ void diag_inv8(const double* A, double* Li, const double* Dinv, int c0) {
-    const int i = threadIdx.x & 63;
-    if (i >= 8) return;
-    double L[8][8], inv[8], x[8];
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-        inv[m] = Dinv[c0 + m];
-#pragma unroll
-        for (int k = 0; k < m; k++) L[m][k] = A[(c0 + m) * LD + c0 + k];
-    }
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-        double s = m == i ? 1.0 : 0.0;
-#pragma unroll
-        for (int k = 0; k < m; k++) s = fma(-L[m][k], x[k], s);
-        x[m] = m >= i ? s * inv[m] : 0.0;
-    }
-#pragma unroll
-    for (int m = 0; m < 8; m++) Li[(c0 + m) * LD + c0 + i] = x[m];
-}
-
-// Block row s (rows 8s .. 8s+7) of Li = L^-1, by one wave, for the column blocks k < s with
-// k = part (mod nparts):  X_ss = L_ss^-1 (diag_inv8; every wave that calls this writes the same
-// bytes) and X_sk = -X_ss sum_{m=k}^{s-1} L_sm X_mk, lane = (row r, column c) of the 8x8 block.
-// Needs the panels <= s factored and X's block rows < s complete: in the potrf step loop block
-// row s is built by waves 1-3 during step s, off the pivot chain, so only block row 7 is left
-// after the last panel (it replaces the 8 -> 16 -> 32 doubling stages, ~27 % of potrf + inverse).
-// scr: 64 doubles of LDS for this wave (the T block between its two products).
-__device__ __forceinline__ void inv_row(const double* A, double* Li, const double* Dinv, int s, int part,
-                                        int nparts, double* scr) {
-    const int lane = threadIdx.x & 63;
-    const int r = lane >> 3, c = lane & 7;
-    const int c0 = 8 * s;
-    diag_inv8(A, Li, Dinv, c0);
-    if (s == 0) return;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    double xs[8];  // row r of X_ss
-#pragma unroll
-    for (int m = 0; m < 8; m++) xs[m] = Li[(c0 + r) * LD + c0 + m];
-    for (int k = part; k < s; k += nparts) {
-        double t = 0.0;
-        for (int m = k; m < s; m++) {
-#pragma unroll
-            for (int q = 0; q < 8; q++) t = fma(A[(c0 + r) * LD + 8 * m + q], Li[(8 * m + q) * LD + 8 * k + c], t);
-        }
-        scr[lane] = t;  // T[r][c]
-        double x = 0.0;
-#pragma unroll
-        for (int m = 0; m < 8; m++) x = fma(xs[m], scr[8 * m + c], x);
-        Li[(c0 + r) * LD + 8 * k + c] = -x;
-    }
-}
-
-// A[I-block rows][J-block cols] -= P_I P_J^T with the panel at columns c0 .. c0+7, for the
-// trailing columns (>= c0 + 8).  Block columns that still hold the panel itself (its 8 columns
-// are the block's first half) get a zero B operand there, so those outputs equal their input and
-// every block is stored whole: no per-element masked stores (a diagonal block's upper triangle
-// takes garbage, which is never read).
-// NB trailing blocks (I[k], J[k]) at once, the blocks with on[k] updated: the two K = 4 MFMAs
-// of a block go to separate accumulators and every block's MFMAs are issued before any result
-// is read, so a step costs one MFMA latency, not one per block and pass.
-template <int NB>
-__device__ __forceinline__ void trail_blocks(double* A, int c0, const int (&I)[NB], const int (&J)[NB],
-                                             const bool (&on)[NB]) {
-    const int lane = threadIdx.x & 63;
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int lo = c0 + 8;
-    d4 c[NB], d[NB];
-    double a0[NB], a1[NB], b0[NB], b1[NB];
-#pragma unroll
-    for (int k = 0; k < NB; k++) {
-        if (!on[k]) continue;
-#pragma unroll
-        for (int e = 0; e < 4; e++) c[k][e] = A[(16 * I[k] + kq + 4 * e) * LD + 16 * J[k] + r16];
-        a0[k] = -A[(16 * I[k] + r16) * LD + c0 + kq];
-        a1[k] = -A[(16 * I[k] + r16) * LD + c0 + 4 + kq];
-        const bool trailing = 16 * J[k] + r16 >= lo;
-        b0[k] = trailing ? A[(16 * J[k] + r16) * LD + c0 + kq] : 0.0;
-        b1[k] = trailing ? A[(16 * J[k] + r16) * LD + c0 + 4 + kq] : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < NB; k++)
-        if (on[k]) c[k] = mfma(a0[k], b0[k], c[k]);
-#pragma unroll
-    for (int k = 0; k < NB; k++)
-        if (on[k]) d[k] = mfma(a1[k], b1[k], d4{0.0, 0.0, 0.0, 0.0});
-#pragma unroll
-    for (int k = 0; k < NB; k++) {
-        if (!on[k]) continue;
-#pragma unroll
-        for (int e = 0; e < 4; e++) A[(16 * I[k] + kq + 4 * e) * LD + 16 * J[k] + r16] = c[k][e] + d[k][e];
-    }
-}
-
-// LL^T of the lower triangle of A (LDS) in place and Li = L^-1 (Li zeroed by the caller).
-// Look-ahead: in step s wave 0 applies panel s to the block column holding panel s+1 and
-// factors panel s+1 right away, while waves 1-3 apply panel s to the block columns right of it
-// and build block row s of the inverse (inv_row); one barrier per step, and the step loop is
-// unrolled, so every step issues only the MFMAs of its live blocks.
-// early: a ready word published once every wave's earlier stores landed (after the first panel
-// step, when they long have), so the caller's stores need no waiting on its critical path
-[[maybe_unused]] __device__ void potrf_inverse(double* A, double* Li, double* Tm, double* Dinv, int* flags, long long* pt,
-                              int* early, int epoch) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    auto pstamp = [&](int slot) {
-        if (pt && tid == 0) pt[slot] = (long long)__builtin_amdgcn_s_memrealtime();
-    };
-    pstamp(0);
-    if (w == 0) panel_factor(A, Dinv, 0, flags);
-    if (early) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (early && tid == 0) __hip_atomic_store(early, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    pstamp(1);
-#pragma unroll
-    for (int s = 0; s + 1 < T / 8; s++) {
-        const int c0 = 8 * s;
-        const int J1 = (c0 + 8) >> 4;  // block column holding panel s+1
-        if (w == 0) {
-            const int I[4] = {0, 1, 2, 3}, J[4] = {J1, J1, J1, J1};
-            const bool on[4] = {0 >= J1, 1 >= J1, 2 >= J1, 3 >= J1};
-            trail_blocks<4>(A, c0, I, J, on);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // own LDS writes before the reads
-#if M3S_DF_STAMPS
-            if (pt && tid == 0) pt[20 + 4 * s] = (long long)__builtin_amdgcn_s_memtime();
-#endif
-            panel_factor(A, Dinv, c0 + 8, flags);
-#if M3S_DF_STAMPS
-            if (pt && tid == 0) pt[21 + 4 * s] = (long long)__builtin_amdgcn_s_memtime();
-#endif
-        } else {
-            const int I[3] = {w, w, w};
-            const int J[3] = {min(J1 + 1, 3), min(J1 + 2, 3), min(J1 + 3, 3)};
-            const bool on[3] = {J1 + 1 <= w, J1 + 2 <= w, J1 + 3 <= w};
-            if (on[0]) trail_blocks<3>(A, c0, I, J, on);
-            inv_row(A, Li, Dinv, s, w - 1, 3, Tm + 64 * w);
-#if M3S_DF_STAMPS
-            if (pt && tid == 192) pt[22 + 4 * s] = (long long)__builtin_amdgcn_s_memtime();
-#endif
-        }
-        __syncthreads();
-#if M3S_DF_STAMPS
-        if (pt && tid == 0) pt[23 + 4 * s] = (long long)__builtin_amdgcn_s_memtime();
-#endif
-        pstamp(2 + s);
-    }
-    inv_row(A, Li, Dinv, T / 8 - 1, w, 4, Tm + 64 * w);  // the last block row of the inverse
-    __syncthreads();
-    pstamp(17);
-}
-
 // ---------------------------------------------------------------------------------------------
-// Column-cyclic LL^T + inverse of the 64x64 tile (M3S_DF_CC=1, default).  Wave w owns columns
-// 16w .. 16w+15, lane = row, in registers.  Column c is factored by its owner (pivot by
-// v_readlane, rsq + one Newton step, scale, then rank-1 updates of the owner's remaining
-// columns by v_readlane broadcasts: no LDS round trip and no barrier on the pivot chain) and
-// published to the LDS column buffer Lc[c][row] with a counter; the later waves apply each
-// published column to their own columns as it arrives (they trail the chain by one LDS hop and
-// catch up while the owner works, since an apply is cheaper than a factor step).  Measured
-// constants (tools/ubench_lat64.hip, gfx950): a dependent f64 VALU op ~5.5 cycles for one wave,
-// an LDS write -> read round trip ~131, a dependent f64 MFMA ~74, a balanced s_barrier ~13 --
-// the pivot chain of the 8-column panel steps (MFMA trailing update + LDS round trips + a barrier
-// per panel) cost ~3x this.
+// LL^T + inverse of the 64x64 tile in registers, lane = row.  A column is factored by its owner
+// wave (pivot by v_readlane, rsq + one Newton step, scale, then rank-1 updates of the batch's
+// remaining columns by v_readlane broadcasts: no LDS round trip and no barrier on the pivot
+// chain) and published through LDS with a counter; the other waves apply what is published to
+// their own columns as it arrives.  Measured constants (tools/ubench_lat64.hip, gfx950): a
+// dependent f64 VALU op ~5.5 cycles for one wave, an LDS write -> read round trip ~131, a
+// dependent f64 MFMA ~74, a balanced s_barrier ~13 -- the pivot chain of the former 8-column
+// panel steps in LDS (MFMA trailing update + LDS round trips + a barrier per panel) cost ~3x this.
 // Each wave then inverts its 16x16 diagonal block, X_ww = [[X_a, 0], [X_ba, X_b]] (two 8x8
-// inverses, diag_inv8, and X_ba = -X_b L_ba X_a by VALU), and builds block column w of
-// Li = L^-1 (see step 3 below) while the later waves still factor.
-// sync (LDS ints): [0] columns published, [1 + w] X_ww written.
+// inverses and X_ba = -X_b L_ba X_a by VALU: diag_inv16), and builds block column w of Li = L^-1.
+// History (each variant is in git history, none is built any more): the 8-column panel factor
+// in LDS, then a column-cyclic register factor (wave w owned columns 16w .. 16w+15 and published
+// them one by one; 10.2 us per tile in the chain), then the batch-cyclic one below (8.0 us).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int lds_wait_geq(int* p, int v, int* flags) {
     int x, spins = 0;
@@ -428,170 +221,30 @@ __device__ __forceinline__ void diag_inv16(const double* A, double* Li, const do
 // LDS ints of the tile factor: [0] columns published, [1 + w] X_ww written, [8 + w] wave w's
 // batches written to the tile (potrf_bc_w)
 constexpr int kDfSync = 12;
-// LDS scratch of potrf_cc (doubles): per wave 64 + a 16x17 block, then per wave a [64][4] batch
-constexpr int kCcScrBase = 4 * 64 + 4 * 16 * 17;
-constexpr int kCcScr = kCcScrBase + 4 * 256;
-template <int W>
-__device__ __forceinline__ void potrf_cc_w(double* A, double* Li, double* Lc, double* scratch, int* sync, double* Dinv,
-                                           int* flags, long long* pt) {
-    const int lane = threadIdx.x & 63;
-    constexpr int C0 = 16 * W;
-    auto wstamp = [&](int k) {
-#if M3S_DF_STAMPS
-        if (pt && lane == 0) pt[8 * W + k] = (long long)__builtin_amdgcn_s_memtime();
-#endif
-    };
-    wstamp(0);
-    double a[16];
-#pragma unroll
-    for (int jj = 0; jj < 16; jj++) a[jj] = A[lane * LD + C0 + jj];
-    // 1. the earlier waves' columns, as they are published: two columns per half-iteration from
-    //    two register buffers, the next pair's LDS loads issued (after polling the counter, when
-    //    the backlog does not already cover them) before the current pair's FMAs.  A runtime
-    //    loop: unrolled, the scheduler hoists every load and spills.
-    if constexpr (W > 0) {
-        int avail = lds_wait_geq(sync, 2, flags);
-        double pa0, pa1, qa0[16], qa1[16], pb0, pb1, qb0[16], qb1[16];
-        auto load = [&](int c, double& p0, double& p1, double (&q0)[16], double (&q1)[16]) {
-            p0 = Lc[c * 64 + lane];
-            p1 = Lc[(c + 1) * 64 + lane];
-#pragma unroll
-            for (int jj = 0; jj < 16; jj++) {
-                q0[jj] = Lc[c * 64 + C0 + jj];
-                q1[jj] = Lc[(c + 1) * 64 + C0 + jj];
-            }
-        };
-        auto apply = [&](double p0, double p1, const double (&q0)[16], const double (&q1)[16]) {
-#pragma unroll
-            for (int jj = 0; jj < 16; jj++) a[jj] = fma(-p1, q1[jj], fma(-p0, q0[jj], a[jj]));
-        };
-        load(0, pa0, pa1, qa0, qa1);
-#pragma unroll 1
-        for (int c = 0; c < C0; c += 4) {
-            if (c + 4 > avail) avail = lds_wait_geq(sync, c + 4, flags);
-            load(c + 2, pb0, pb1, qb0, qb1);
-            apply(pa0, pa1, qa0, qa1);
-            if (c + 4 < C0) {
-                if (c + 6 > avail) avail = lds_wait_geq(sync, c + 6, flags);
-                load(c + 4, pa0, pa1, qa0, qa1);
-            }
-            apply(pb0, pb1, qb0, qb1);
-        }
-    }
-    wstamp(1);
-    // 2. the own columns: the pivot chain, in batches of 4 columns.  Inside a batch each pivot
-    //    updates the batch's later columns by v_readlane (on the chain); after a batch, its
-    //    rank-4 update of the wave's remaining columns reads the 4 values of each target row from
-    //    a row-major copy of the batch (two uniform ds_read_b128 + 4 FMAs per column instead of
-    //    4 x (2 v_readlane + FMA): the owner's issue is what bounds its per-column time)
-    double y[16];
-    bool bad = false;
-    double* Lr = scratch + kCcScrBase + 256 * W;  // this wave's batch, row-major [64][4]
-#pragma unroll
-    for (int ib = 0; ib < 4; ib++) {
-#pragma unroll
-        for (int p = 0; p < 4; p++) {
-            const int jj = 4 * ib + p, c = C0 + jj;
-            const double d = rdlane(a[jj], c);
-            bad |= d <= 0.0;  // SimplicialLLT: fails iff a pivot <= 0 (NaN passes)
-            double r = __builtin_amdgcn_rsq(d);
-            r = r * fma(-0.5 * d * r, r, 1.5);
-            y[jj] = r;
-            a[jj] *= r;
-            if (W < 3) {
-                Lc[c * 64 + lane] = a[jj];
-                lds_publish(sync, c + 1);
-            }
-#pragma unroll
-            for (int q = p + 1; q < 4; q++) a[4 * ib + q] = fma(-a[jj], rdlane(a[jj], C0 + 4 * ib + q), a[4 * ib + q]);
-        }
-        if (ib < 3) {
-            const int NQ = 12 - 4 * ib;  // this batch's target columns: all loaded, then used
-#pragma unroll
-            for (int p = 0; p < 4; p++) Lr[lane * 4 + p] = a[4 * ib + p];
-            double v[12][4];
-#pragma unroll
-            for (int q = 0; q < 12; q++)
-                if (q < NQ) {
-#pragma unroll
-                    for (int p = 0; p < 4; p++) v[q][p] = Lr[(C0 + 4 * ib + 4 + q) * 4 + p];
-                }
-#pragma unroll
-            for (int q = 0; q < 12; q++)
-                if (q < NQ)
-#pragma unroll
-                for (int p = 0; p < 4; p++) a[4 * ib + 4 + q] = fma(-a[4 * ib + p], v[q][p], a[4 * ib + 4 + q]);
-        }
-    }
-    // L back into the tile (every lane: rows above the pivots write upper-triangle garbage,
-    // never read), 1 / l_pp for the inverse
-#pragma unroll
-    for (int jj = 0; jj < 16; jj++) A[lane * LD + C0 + jj] = a[jj];
-    if (lane == 0) {
-        if (bad) flags[kFlagFail] = 1;
-#pragma unroll
-        for (int jj = 0; jj < 16; jj++) Dinv[C0 + jj] = y[jj];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    // 3. the inverse: X_WW (diagonal block), flagged; then block column W of X, column-oriented:
-    //    X_VW = -X_VV sum_{m=W}^{V-1} L_Vm X_mW for V > W -- the sums need only L (Lc) and this
-    //    wave's own earlier blocks, so each is ready before X_VV is flagged and the tail after the
-    //    last column is wave 3's X_33 plus one 16x16 product per column block
-    double* scr = scratch + 64 * W;               // this wave's scratch
-    double* sT = scratch + 4 * 64 + 16 * 17 * W;  // ... and its 16 x 17 block
-    wstamp(2);
-    diag_inv16(A, Li, Dinv, C0, scr);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    lds_publish(sync + 1 + W, 1);
-    wstamp(3);
-    const int r16 = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int V = W + 1; V < 4; V++) {
-        lds_wait_geq(sync, 16 * V, flags);  // L_Vm, m < V: the columns of blocks < V published
-        d4 acc[4];
-#pragma unroll
-        for (int m = W; m < V; m++) {
-            acc[m] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int st = 0; st < 4; st++)
-                acc[m] = mfma(Lc[(16 * m + 4 * st + kq) * 64 + 16 * V + r16],
-                              Li[(16 * m + 4 * st + kq) * LD + C0 + r16], acc[m]);
-        }
-        d4 t = acc[W];
-#pragma unroll
-        for (int m = W + 1; m < V; m++) t += acc[m];
-#pragma unroll
-        for (int e = 0; e < 4; e++) sT[(kq + 4 * e) * 17 + r16] = t[e];
-        lds_wait_geq(sync + 1 + V, 1, flags);  // X_VV
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        d4 x = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int st = 0; st < 4; st++)
-            x = mfma(-Li[(16 * V + r16) * LD + 16 * V + 4 * st + kq], sT[(4 * st + kq) * 17 + r16], x);
-#pragma unroll
-        for (int e = 0; e < 4; e++) Li[(16 * V + kq + 4 * e) * LD + C0 + r16] = x[e];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // X_VW before the next V's sum reads it
-        wstamp(4 + V - W - 1);
-    }
-}
+// LDS scratch of potrf_bc (doubles): per wave 64 + a 16x17 block.  (The 4 * 256 after them were
+// the column-cyclic factor's per-wave batch copies: unused now, kept so that the kernel's LDS
+// size is what it was.)
+constexpr int kBcScr = 4 * 64 + 4 * 16 * 17 + 4 * 256;
+constexpr int kBatchCols = 4;  // columns per batch of potrf_bc_w (8 measured slower, below)
 
-// Batch-cyclic variant (M3S_DF_BC=1): the tile's 16 batches of 4 columns go round-robin to the
-// 4 waves (batch b -> wave b % 4; wave w holds columns 16 lb + 4 w + p in registers, lane = row).
-// The owner of batch b applies batch b-1 to its 4 columns only, factors them (pivots by
-// v_readlane, as potrf_cc) and publishes them as a row-major [64][4] copy (Lb + 256 b; the
-// consumers read a target row's 4 values with two uniform ds_read_b128) plus into the tile (the
-// inverse reads L there); every wave applies each published batch to its own later columns off
-// the critical path.  The pivot chain thus hands over every 4 columns instead of every 16, and
-// between two of its columns the owner issues 4 FMAs of rank-4 update instead of the whole
-// 16-column block's -- the owner's issue, not the hand-off, bounded potrf_cc (~260 cycles per
-// column).  The inverse (X_WW by wave W, then the column-block products) follows the last batch;
-// it reads L from the tile, which each wave writes after its publish (off the critical path) and
-// announces on its own counter (sync[8 + w]: batches written).  Measured (ubench_potrf64 /
-// ubench_chol_df, profiles/r04_ak_*): ~940 cycles per batch hand-off + factor, tile factor +
-// inverse 8.0 us vs potrf_cc's 10.2 us in the chain; 8-column batches (M3S_DF_BC_W=8) 9.6 us.
-template <int W, int BW>
+// Batch-cyclic: the tile's 16 batches of 4 columns go round-robin to the 4 waves (batch b -> wave
+// b % 4; wave w holds columns 16 lb + 4 w + p in registers, lane = row).  The owner of batch b
+// applies batch b-1 to its 4 columns only, factors them (pivots by v_readlane) and publishes them
+// as a row-major [64][4] copy (Lb + 256 b; the consumers read a target row's 4 values with two
+// uniform ds_read_b128) plus into the tile (the inverse reads L there); every wave applies each
+// published batch to its own later columns off the critical path.  The pivot chain thus hands
+// over every 4 columns instead of every 16, and between two of its columns the owner issues 4
+// FMAs of rank-4 update instead of the whole 16-column block's -- the owner's issue, not the
+// hand-off, bounded the column-cyclic factor (~260 cycles per column).  The inverse (X_WW by
+// wave W, then the column-block products) follows the last batch; it reads L from the tile, which
+// each wave writes after its publish (off the critical path) and announces on its own counter
+// (sync[8 + w]: batches written).  Measured (ubench_potrf64 / ubench_chol_df, profiles/r04_ak_*):
+// ~940 cycles per batch hand-off + factor, tile factor + inverse 8.0 us vs the column-cyclic
+// factor's 10.2 us in the chain; 8-column batches 9.6 us.
+template <int W>
 __device__ __forceinline__ void potrf_bc_w(double* A, double* Li, double* Lb, double* scratch, int* sync, double* Dinv,
                                            int* flags, long long* pt) {
+    constexpr int BW = kBatchCols;
     constexpr int NL = 16 / BW;  // local batches per wave
     const int lane = threadIdx.x & 63;
     auto wstamp = [&](int k) {
@@ -687,7 +340,6 @@ __device__ __forceinline__ void potrf_bc_w(double* A, double* Li, double* Lb, do
             apply(next, lb, NL);
         }
         if (nb >= 1) {  // the previous batch: to this batch's columns first (the critical path)
-#if M3S_DF_BC_SPEC
             // the counter and the batch's values read together, the values kept once the counter
             // shows the batch published (the producer stored them before the counter, and a wave's
             // LDS reads execute in order): one LDS round trip per hand-off instead of two (wait +
@@ -722,11 +374,6 @@ __device__ __forceinline__ void potrf_bc_w(double* A, double* Li, double* Lb, do
                 }
                 a[BW * lb + p] = v;
             }
-#else
-            lds_wait_geq(sync, BW * nb, flags);
-            bstamp(2 * nb);
-            apply(nb - 1, lb, lb + 1);
-#endif
             bstamp(2 * nb + 1);
         }
         // factor the batch: pivot chain inside it by v_readlane.  (Reading the batch's diagonal
@@ -773,16 +420,15 @@ __device__ __forceinline__ void potrf_bc_w(double* A, double* Li, double* Lb, do
         next = nb + 1;
     }
     if (lane == 0 && bad) flags[kFlagFail] = 1;
-    // the inverse, as potrf_cc's step 3, with L read from the tile
+    // the inverse: X_WW (diagonal block), flagged; then block column W of X, with L read from the tile
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     diag_block();
     const int r16 = lane & 15, kq = lane >> 4;
-#if M3S_DF_BC_RL
     // block column W of Li, right-looking: once X_mW is known, its products L_Vm X_mW go into
     // every later block row's accumulator (t_V = sum_m L_Vm X_mW), the next row's first; then
     // X_{m+1,W} = -X_{m+1,m+1} t_{m+1}.  Only the last product waits on X_33, instead of the whole
     // t_3W (up to 12 MFMAs) being issued after X_20 / X_21.  The same products summed in another
-    // order than the left-looking form below (the acc[m] chains added in m order): not bitwise.
+    // order than the former left-looking form (per-m chains added in m order): not bitwise.
     // (L's block column m is in the tile: for m = W diag_block waited for it, for m > W the wave
     // that published X_mm did.)
     d4 acc[4];
@@ -808,57 +454,19 @@ __device__ __forceinline__ void potrf_bc_w(double* A, double* Li, double* Lb, do
         for (int e = 0; e < 4; e++) Li[(16 * V + kq + 4 * e) * LD + C0 + r16] = x[e];
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-#pragma unroll
-    for (int V = W + 1; V < 4; V++) {
-        wait_written(16 * V);
-        d4 acc[4];
-#pragma unroll
-        for (int m = W; m < V; m++) {
-            acc[m] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int st = 0; st < 4; st++)
-                acc[m] = mfma(A[(16 * V + r16) * LD + 16 * m + 4 * st + kq], Li[(16 * m + 4 * st + kq) * LD + C0 + r16],
-                              acc[m]);
-        }
-        d4 t = acc[W];
-#pragma unroll
-        for (int m = W + 1; m < V; m++) t += acc[m];
-#pragma unroll
-        for (int e = 0; e < 4; e++) sT[(kq + 4 * e) * 17 + r16] = t[e];
-        lds_wait_geq(sync + 1 + V, 1, flags);  // X_VV
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        d4 x = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int st = 0; st < 4; st++)
-            x = mfma(-Li[(16 * V + r16) * LD + 16 * V + 4 * st + kq], sT[(4 * st + kq) * 17 + r16], x);
-#pragma unroll
-        for (int e = 0; e < 4; e++) Li[(16 * V + kq + 4 * e) * LD + C0 + r16] = x[e];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-#endif
     wstamp(6);
 }
 
-// the register factor + inverse of the tile: batch-cyclic (potrf_bc_w, M3S_DF_BC=1, default) or
-// column-cyclic (potrf_cc_w); sync[0 .. kDfSync) zeroed and visible
-__device__ __forceinline__ void potrf_cc(double* A, double* Li, double* Lc, double* scratch, int* sync, double* Dinv,
+// the register factor + inverse of the tile: every wave its potrf_bc_w; sync[0 .. kDfSync) zeroed
+// and visible
+__device__ __forceinline__ void potrf_bc(double* A, double* Li, double* Lb, double* scratch, int* sync, double* Dinv,
                                          int* flags, long long* pt = nullptr) {
-#if M3S_DF_BC
     switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {
-        case 0: potrf_bc_w<0, M3S_DF_BC_W>(A, Li, Lc, scratch, sync, Dinv, flags, pt); break;
-        case 1: potrf_bc_w<1, M3S_DF_BC_W>(A, Li, Lc, scratch, sync, Dinv, flags, pt); break;
-        case 2: potrf_bc_w<2, M3S_DF_BC_W>(A, Li, Lc, scratch, sync, Dinv, flags, pt); break;
-        default: potrf_bc_w<3, M3S_DF_BC_W>(A, Li, Lc, scratch, sync, Dinv, flags, pt); break;
+        case 0: potrf_bc_w<0>(A, Li, Lb, scratch, sync, Dinv, flags, pt); break;
+        case 1: potrf_bc_w<1>(A, Li, Lb, scratch, sync, Dinv, flags, pt); break;
+        case 2: potrf_bc_w<2>(A, Li, Lb, scratch, sync, Dinv, flags, pt); break;
+        default: potrf_bc_w<3>(A, Li, Lb, scratch, sync, Dinv, flags, pt); break;
     }
-#else
-    switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {
-        case 0: potrf_cc_w<0>(A, Li, Lc, scratch, sync, Dinv, flags, pt); break;
-        case 1: potrf_cc_w<1>(A, Li, Lc, scratch, sync, Dinv, flags, pt); break;
-        case 2: potrf_cc_w<2>(A, Li, Lc, scratch, sync, Dinv, flags, pt); break;
-        default: potrf_cc_w<3>(A, Li, Lc, scratch, sync, Dinv, flags, pt); break;
-    }
-#endif
     __syncthreads();
 }
 
@@ -1150,7 +758,7 @@ __global__ __launch_bounds__(NT) void chol_df_kernel(DfArgs a) {
     __shared__ __attribute__((aligned(16))) double Y[T * LD];
     __shared__ __attribute__((aligned(16))) double Z[T * LD];
     __shared__ double Dinv[T];
-    __shared__ double Scr[kCcScr];
+    __shared__ double Scr[kBcScr];
     __shared__ int Sync[kDfSync];
     const int tid = threadIdx.x;
     const int nt = a.nt;
@@ -1240,10 +848,7 @@ __global__ __launch_bounds__(NT) void chol_df_kernel(DfArgs a) {
                 store_acc_coh(tile(j, j - 1), ld, accs);
                 lds_barrier();  // the GEMM's reads of X and Y are done (the stores stay in flight)
                 acc_to_lds(X, accs);
-#if !M3S_DF_CC
-                for (int id = tid; id < T * LD; id += NT) Y[id] = 0.0;  // Linv_{j-1} read: Y -> the new Li
-#endif
-                // (potrf_cc writes every block of Li it reads -- the diagonal and lower 16x16 blocks --
+                // (potrf_bc writes every block of Li it reads -- the diagonal and lower 16x16 blocks --
                 // and the Linv store below writes the upper ones as zeros: no zeroing pass on the chain)
                 if (tid < kDfSync) Sync[tid] = 0;
                 lds_barrier();
@@ -1254,14 +859,9 @@ __global__ __launch_bounds__(NT) void chol_df_kernel(DfArgs a) {
                 fstamp(j, 3);
             }
             cstamp(j, 1);
-#if M3S_DF_CC
             if (j >= 1 && tid == 0)  // L_{j,j-1}: every wave waited for its stores before the barrier
                 __hip_atomic_store(a.ready + j * nt + (j - 1), a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            potrf_cc(Z, Y, X, Scr, Sync, Dinv, a.flags);  // X (L_{j,j-1}) is free: the column buffer
-#else
-            potrf_inverse(Z, Y, X, Dinv, a.flags, a.trace && j == 0 ? a.trace + 4 * a.ntiles : nullptr,
-                          j >= 1 ? a.ready + j * nt + (j - 1) : nullptr, a.epoch);
-#endif
+            potrf_bc(Z, Y, X, Scr, Sync, Dinv, a.flags);  // X (L_{j,j-1}) is free: the batch buffer
             cstamp(j, 2);
             double* Lk = a.Linv + (int64_t)j * T * T;
 #pragma unroll

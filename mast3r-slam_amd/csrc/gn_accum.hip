@@ -23,105 +23,68 @@
 #include "sim3.h"
 #include "wave_reduce.h"
 
-// Scheduling of the 4 points of a lane's step (AccStage::compute): 0 (default; what every
-// measurement so far ran -- the old default of 1 sat below its first use and never applied) lets
-// the compiler interleave the points freely, 1 fences after every point (one point's temporaries
-// live at a time), 2 after every second point.
-#ifndef M3S_ACC_SCHED_BARRIER
-#define M3S_ACC_SCHED_BARRIER 0
-#endif
-// Diagnostics builds only (tools/build_variants.sh; the results are NOT the normal equations):
-// 1 = the packed accumulate's compute alone, 2 = its memory traffic alone.
-#ifndef M3S_ACC_DIAG
-#define M3S_ACC_DIAG 0
-#endif
-
 namespace m3s {
 
 // ---------------------------------------------------------------------------
-// Point math, one point-edge per call, generic in the value type V (float here; a packed
-// float2 pair variant was measured: on gfx950 a v_pk_*_f32 op costs the SIMD twice the cycles
-// of a scalar one, so pairs only save issue slots while doubling the accumulator VGPRs
-// (144 vs 92, 3 vs 5 waves/SIMD) and ran 10 % slower -- the kernel is latency-bound).
+// Point math, one point-edge per call, in plain float (a packed float2 pair variant was
+// measured: on gfx950 a v_pk_*_f32 op costs the SIMD twice the cycles of a scalar one, so pairs
+// only save issue slots while doubling the accumulator VGPRs (144 vs 92, 3 vs 5 waves/SIMD) and
+// ran 10 % slower -- the kernel is latency-bound).
 // ---------------------------------------------------------------------------
-template <typename V>
-struct VMask {
-    typedef bool type;
-};
-
-__device__ __forceinline__ float vfma(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ float vsplat(float s, float) { return s; }
 __device__ __forceinline__ float vrcp(float a) { return __builtin_amdgcn_rcpf(a); }    // v_rcp_f32
+// rays mode normalises with the hardware v_sqrt_f32 / v_rcp_f32 (1 ulp).  Measured against a
+// correctly rounded sqrtf and v_rcp_f32 + one Newton step (the reference's sqrtf / 1.0/x are
+// correctly rounded) and against v_rsq_f32 + one Newton step (tools/accuracy_probe.py,
+// profiles/r03_rays_norm_ab.json): the first GN step of cfg4 lands 2.13e-5 / 2.11e-5 / 2.16e-5
+// (of max |dx|) from the exactly summed system -- the per-point ulp errors average out in the
+// 4e8-term sums -- while the two others cost 16 % / 13 % accumulate time.
 __device__ __forceinline__ float vsqrt(float a) { return __builtin_amdgcn_sqrtf(a); }  // normal or 0 inputs
+__device__ __forceinline__ float vlog2(float a) { return __builtin_amdgcn_logf(a); }   // inputs > z_eps
 // sqrt(q) of the point records: correctly rounded, as the reference's sqrtf(conf_weight)
 // (gn_kernels.cu:1404-1405; nvcc's sqrtf is IEEE).  Computed once per call (the record builders:
 // the pack, the first accumulate, the unpacked path of 1-2 iteration calls), so the ~10 extra
 // VALU of the exact expansion are off the iteration kernel.
 __device__ __forceinline__ float sqrt_cr(float a) { return __builtin_sqrtf(a); }
-__device__ __forceinline__ float vlog2(float a) { return __builtin_amdgcn_logf(a); }   // inputs > z_eps
-// rays mode's normalisation (M3S_RAYS_CR): 0 (default) = the hardware v_sqrt_f32 / v_rcp_f32
-// (1 ulp); 1 = correctly rounded sqrtf and v_rcp_f32 + one Newton step (the reference's sqrtf /
-// 1.0/x are correctly rounded); 2 = v_rsq_f32 + one Newton step.  Measured (tools/
-// accuracy_probe.py, profiles/r03_rays_norm_ab.json): the first GN step of cfg4 lands 2.13e-5 /
-// 2.11e-5 / 2.16e-5 (of max |dx|) from the exactly summed system with 0 / 1 / 2 -- the per-point
-// ulp errors average out in the 4e8-term sums -- while 1 and 2 cost 16 % / 13 % accumulate time.
-#ifndef M3S_RAYS_CR
-#define M3S_RAYS_CR 0
-#endif
-__device__ __forceinline__ float vrcp_nr(float a) {
-    const float r = __builtin_amdgcn_rcpf(a);
-    return fmaf(fmaf(-a, r, 1.0f), r, r);
-}
-// 1/sqrt(a): v_rsq_f32 plus one Newton step y (1.5 - 0.5 a y^2) (~0.5 ulp)
-__device__ __forceinline__ float vrsq_nr(float a) {
-    const float y = __builtin_amdgcn_rsqf(a);
-    const float h = 0.5f * a * y;
-    return fmaf(fmaf(-h, y, 0.5f), y, y);
-}
-__device__ __forceinline__ float vabs(float a) { return fabsf(a); }
-__device__ __forceinline__ float vmin(float a, float b) { return fminf(a, b); }
-__device__ __forceinline__ float vsel(bool m, float a, float b) { return m ? a : b; }
-__device__ __forceinline__ bool vgt(float a, float b) { return a > b; }
-__device__ __forceinline__ bool vlt(float a, float b) { return a < b; }
-__device__ __forceinline__ bool vand(bool a, bool b) { return a && b; }
+// a && b with both sides evaluated first (a call's arguments): the validity conjunctions below
+// stay compares and mask operations.  Spelled inline, && short-circuits and & on bools regroups
+// the compares: either changes the generated code.
+__device__ __forceinline__ bool both(bool a, bool b) { return a && b; }
 
 // Huber weight (gn_kernels.cu:172-175): |r| < 1.345 ? 1 : 1.345/|r| as a compare-select, so a
 // NaN residual gives a NaN weight like the reference (a min(1, .) form turns it into 1); the
 // reciprocal is v_rcp_f32 (1 ulp; DESIGN.md §2 measures what that costs).
-template <typename V>
-__device__ __forceinline__ V huber(V r) {
-    const V a = vabs(r);
-    return vsel(vlt(a, 1.345f), vsplat(1.0f, r), vsplat(1.345f, r) * vrcp(a));
+__device__ __forceinline__ float huber(float r) {
+    const float a = fabsf(r);
+    return a < 1.345f ? 1.0f : 1.345f * vrcp(a);
 }
 
 // Accumulate one raw Jacobian row r (compile-time nonzero mask) with weight w, residual e.
-template <int MASK, typename V>
-__device__ __forceinline__ void acc_row(V* __restrict__ acc, const V* r, V w, V e) {
-    V wr[7];
+template <int MASK>
+__device__ __forceinline__ void acc_row(float* __restrict__ acc, const float* r, float w, float e) {
+    float wr[7];
 #pragma unroll
-    for (int a = 0; a < 7; a++) wr[a] = (MASK >> a & 1) ? w * r[a] : V(0.0f);
+    for (int a = 0; a < 7; a++) wr[a] = (MASK >> a & 1) ? w * r[a] : 0.0f;
 #pragma unroll
     for (int a = 0; a < 7; a++) {
         if (!(MASK >> a & 1)) continue;
 #pragma unroll
         for (int b = a; b < 7; b++) {
             if (!(MASK >> b & 1)) continue;
-            acc[sym_idx(a, b)] = vfma(wr[a], r[b], acc[sym_idx(a, b)]);
+            acc[sym_idx(a, b)] = fmaf(wr[a], r[b], acc[sym_idx(a, b)]);
         }
     }
 #pragma unroll
     for (int a = 0; a < 7; a++)
-        if (MASK >> a & 1) acc[28 + a] = vfma(wr[a], e, acc[28 + a]);
+        if (MASK >> a & 1) acc[28 + a] = fmaf(wr[a], e, acc[28 + a]);
 }
 
-template <typename V>
 struct PointsIn {
     // calib: xi2 carries the matched point's INVERSE depth, (z > z_eps) ? v_rcp_f32(z) : NaN (the
     // packed path gathers it precomputed per call, gn_depth_kernel; NaN encodes z <= z_eps)
-    V xi0, xi1, xi2, xj0, xj1, xj2;
-    V sq;                            // sqrt(q)
-    typename VMask<V>::type valid;   // match & q > Q_thresh & ci > C_thresh & cj > C_thresh
-    V ut, vt;  // calib: pixel of the match, (ind % W, ind / W) as float
+    float xi0, xi1, xi2, xj0, xj1, xj2;
+    float sq;      // sqrt(q)
+    bool valid;    // match & q > Q_thresh & ci > C_thresh & cj > C_thresh
+    float ut, vt;  // calib: pixel of the match, (ind % W, ind / W) as float
 };
 
 // T_ij as the 3x4 affine map it applies to a point.  The reference's act_so3
@@ -162,174 +125,142 @@ __device__ __forceinline__ RelXf rel_xf(const Sim3f& T) {
     return R;
 }
 
-template <typename V>
-__device__ __forceinline__ void apply_rel(const RelXf& T, V x0, V x1, V x2, V& X0, V& X1, V& X2) {
-    X0 = vfma(vsplat(T.m[0], x0), x0, vfma(vsplat(T.m[1], x0), x1, vfma(vsplat(T.m[2], x0), x2, vsplat(T.t[0], x0))));
-    X1 = vfma(vsplat(T.m[3], x0), x0, vfma(vsplat(T.m[4], x0), x1, vfma(vsplat(T.m[5], x0), x2, vsplat(T.t[1], x0))));
-    X2 = vfma(vsplat(T.m[6], x0), x0, vfma(vsplat(T.m[7], x0), x1, vfma(vsplat(T.m[8], x0), x2, vsplat(T.t[2], x0))));
+__device__ __forceinline__ void apply_rel(const RelXf& T, float x0, float x1, float x2, float& X0, float& X1,
+                                          float& X2) {
+    X0 = fmaf(T.m[0], x0, fmaf(T.m[1], x1, fmaf(T.m[2], x2, T.t[0])));
+    X1 = fmaf(T.m[3], x0, fmaf(T.m[4], x1, fmaf(T.m[5], x2, T.t[1])));
+    X2 = fmaf(T.m[6], x0, fmaf(T.m[7], x1, fmaf(T.m[8], x2, T.t[2])));
 }
 
-// One (pair of) point-edge(s) from its transformed point X = T_ij Xj: residuals, robust
+// One point-edge from its transformed point X = T_ij Xj: residuals, robust
 // weights, raw rows -> acc.
-template <int MODE, typename V>
-__device__ __forceinline__ void point_body_x(const PointsIn<V>& p, V X0, V X1, V X2, const AccParams& P,
-                                             V* __restrict__ acc) {
-    auto valid = p.valid;
-    const V zero = vsplat(0.0f, X0);
-    const V sq = p.sq;
+template <int MODE>
+__device__ __forceinline__ void point_body_x(const PointsIn& p, float X0, float X1, float X2, const AccParams& P,
+                                             float* __restrict__ acc) {
+    bool valid = p.valid;
+    const float zero = 0.0f;
+    const float sq = p.sq;
 
     if constexpr (MODE == GN_RAYS) {
         // gn_kernels.cu:924-1089
-        const V n2i = vfma(p.xi0, p.xi0, vfma(p.xi1, p.xi1, p.xi2 * p.xi2));
-        const V n2j = vfma(X0, X0, vfma(X1, X1, X2 * X2));
-#if M3S_RAYS_CR == 1
-        const V n1i = __builtin_sqrtf(n2i);
-        const V n1i_inv = vrcp_nr(n1i);
-        const V n1j = __builtin_sqrtf(n2j);
-        const V n1j_inv = vrcp_nr(n1j);
-#elif M3S_RAYS_CR == 2
-        const V n1i_inv = vrsq_nr(n2i);
-        const V n1i = n2i * n1i_inv;
-        const V n1j_inv = vrsq_nr(n2j);
-        const V n1j = n2j * n1j_inv;
-#else
-        const V n1i = vsqrt(n2i);
-        const V n1i_inv = vrcp(n1i);
-        const V n1j = vsqrt(n2j);
-        const V n1j_inv = vrcp(n1j);
-#endif
-        const V rx = n1j_inv * X0, ry = n1j_inv * X1, rz = n1j_inv * X2;
-        const V e0 = rx - n1i_inv * p.xi0;
-        const V e1 = ry - n1i_inv * p.xi1;
-        const V e2 = rz - n1i_inv * p.xi2;
-        const V e3 = n1j - n1i;
+        const float n2i = fmaf(p.xi0, p.xi0, fmaf(p.xi1, p.xi1, p.xi2 * p.xi2));
+        const float n2j = fmaf(X0, X0, fmaf(X1, X1, X2 * X2));
+        const float n1i = vsqrt(n2i);
+        const float n1i_inv = vrcp(n1i);
+        const float n1j = vsqrt(n2j);
+        const float n1j_inv = vrcp(n1j);
+        const float rx = n1j_inv * X0, ry = n1j_inv * X1, rz = n1j_inv * X2;
+        const float e0 = rx - n1i_inv * p.xi0;
+        const float e1 = ry - n1i_inv * p.xi1;
+        const float e2 = rz - n1i_inv * p.xi2;
+        const float e3 = n1j - n1i;
         // one select for both weights: (1/sigma) * 0 = +0 for a finite positive 1/sigma, the bits of
         // selecting each product
-        const V sqv = vsel(valid, sq, zero);
-        const V swr = vsplat(P.s0_inv, sq) * sqv;
-        const V swd = vsplat(P.s1_inv, sq) * sqv;
-        const V wcr = swr * swr, wcd = swd * swd;
-        const V w0 = huber(swr * e0) * wcr;
-        const V w1 = huber(swr * e1) * wcr;
-        const V w2 = huber(swr * e2) * wcr;
-        const V w3 = huber(swd * e3) * wcd;
-#if M3S_RAYS_CR == 2
-        const V n3 = n1j_inv * n1j_inv * n1j_inv;
-#elif M3S_RAYS_CR
-        const V n3 = n1j_inv * vrcp_nr(n2j);
-#else
-        const V n3 = n1j_inv * vrcp(n2j);
-#endif
-        const V dxx = n1j_inv - X0 * X0 * n3;
-        const V dyy = n1j_inv - X1 * X1 * n3;
-        const V dzz = n1j_inv - X2 * X2 * n3;
-        const V dxy = -X0 * X1 * n3;
-        const V dxz = -X0 * X2 * n3;
-        const V dyz = -X1 * X2 * n3;
+        const float sqv = valid ? sq : zero;
+        const float swr = P.s0_inv * sqv;
+        const float swd = P.s1_inv * sqv;
+        const float wcr = swr * swr, wcd = swd * swd;
+        const float w0 = huber(swr * e0) * wcr;
+        const float w1 = huber(swr * e1) * wcr;
+        const float w2 = huber(swr * e2) * wcr;
+        const float w3 = huber(swd * e3) * wcd;
+        const float n3 = n1j_inv * vrcp(n2j);
+        const float dxx = n1j_inv - X0 * X0 * n3;
+        const float dyy = n1j_inv - X1 * X1 * n3;
+        const float dzz = n1j_inv - X2 * X2 * n3;
+        const float dxy = -X0 * X1 * n3;
+        const float dxz = -X0 * X2 * n3;
+        const float dyz = -X1 * X2 * n3;
         {
-            const V r[7] = {dxx, dxy, dxz, zero, rz, -ry, zero};
+            const float r[7] = {dxx, dxy, dxz, zero, rz, -ry, zero};
             acc_row<0b0110111>(acc, r, w0, e0);
         }
         {
-            const V r[7] = {dxy, dyy, dyz, -rz, zero, rx, zero};
+            const float r[7] = {dxy, dyy, dyz, -rz, zero, rx, zero};
             acc_row<0b0101111>(acc, r, w1, e1);
         }
         {
-            const V r[7] = {dxz, dyz, dzz, ry, -rx, zero, zero};
+            const float r[7] = {dxz, dyz, dzz, ry, -rx, zero, zero};
             acc_row<0b0011111>(acc, r, w2, e2);
         }
         {
-            const V r[7] = {rx, ry, rz, zero, zero, zero, n1j};
+            const float r[7] = {rx, ry, rz, zero, zero, zero, n1j};
             acc_row<0b1000111>(acc, r, w3, e3);
         }
     } else if constexpr (MODE == GN_CALIB) {
         // gn_kernels.cu:1360-1495
-        const auto valid_z = vand(vgt(X2, P.z_eps), p.xi2 == p.xi2);  // zi > z_eps <=> 1/zi not NaN
-        const V zj_inv = vsel(valid_z, vrcp(X2), zero);
+        const bool valid_z = both(X2 > P.z_eps, p.xi2 == p.xi2);  // zi > z_eps <=> 1/zi not NaN
+        const float zj_inv = valid_z ? vrcp(X2) : zero;
         // log(zj) - log(zi) (gn_kernels.cu:1385-1390) as ln2 * log2(zj / zi): the residual is a
         // small difference of two ~unit logs, so one log of the ratio keeps it to ~1e-7
         // relative where two float logs lose ~1e-4 of it to cancellation (inf/NaN still
         // propagate: 1/inf = 0 -> -inf).
-        const V e2 = vsel(valid_z, vsplat(0.69314718055994531f, X2) * vlog2(X2 * p.xi2), zero);
-        const V x = X0 * zj_inv, y = X1 * zj_inv;
-        const V u = vfma(vsplat(P.fx, x), x, vsplat(P.cx, x));
-        const V v = vfma(vsplat(P.fy, y), y, vsplat(P.cy, y));
-        valid = vand(vand(valid, valid_z),
-                     vand(vand(vgt(u, P.pb_lo), vlt(u, P.pb_hi_u)), vand(vgt(v, P.pb_lo), vlt(v, P.pb_hi_v))));
-        const V e0 = u - p.ut;
-        const V e1 = v - p.vt;
+        const float e2 = valid_z ? 0.69314718055994531f * vlog2(X2 * p.xi2) : zero;
+        const float x = X0 * zj_inv, y = X1 * zj_inv;
+        const float u = fmaf(P.fx, x, P.cx);
+        const float v = fmaf(P.fy, y, P.cy);
+        valid = both(both(valid, valid_z),
+                     both(both(u > P.pb_lo, u < P.pb_hi_u), both(v > P.pb_lo, v < P.pb_hi_v)));
+        const float e0 = u - p.ut;
+        const float e1 = v - p.vt;
         // one select for both weights: (1/sigma) * 0 = +0 for a finite positive 1/sigma, the bits of
         // selecting each product
-        const V sqv = vsel(valid, sq, zero);
-        const V swp = vsplat(P.s0_inv, sq) * sqv;
-        const V swd = vsplat(P.s1_inv, sq) * sqv;
-        const V wcp = swp * swp, wcd = swd * swd;
-        const V w0 = huber(swp * e0) * wcp;
-        const V w1 = huber(swp * e1) * wcp;
-        const V w2 = huber(swd * e2) * wcd;
-        const V one = vsplat(1.0f, x);
-        const V xz = x * zj_inv, yz = y * zj_inv, xy = x * y;
-#ifndef M3S_CALIB_FOLD_F
-#define M3S_CALIB_FOLD_F 1
-#endif
-#if M3S_CALIB_FOLD_F
+        const float sqv = valid ? sq : zero;
+        const float swp = P.s0_inv * sqv;
+        const float swd = P.s1_inv * sqv;
+        const float wcp = swp * swp, wcd = swd * swd;
+        const float w0 = huber(swp * e0) * wcp;
+        const float w1 = huber(swp * e1) * wcp;
+        const float w2 = huber(swd * e2) * wcd;
+        const float one = 1.0f;
+        const float xz = x * zj_inv, yz = y * zj_inv, xy = x * y;
         // the pixel rows are f * r' (r' = the normalised-plane row): w r r^T = (w f^2) r' r'^T and
         // w r e = (w f^2) r' (e / f), so the focal lengths fold into the weight and the residual
         // (2 multiplies per row instead of 5)
         const float fx2 = P.fx * P.fx, fy2 = P.fy * P.fy, fx_inv = 1.0f / P.fx, fy_inv = 1.0f / P.fy;
         {
-            const V r[7] = {zj_inv, zero, -xz, -xy, vfma(x, x, one), -y, zero};
-            acc_row<0b0111101>(acc, r, w0 * vsplat(fx2, x), e0 * vsplat(fx_inv, x));
+            const float r[7] = {zj_inv, zero, -xz, -xy, fmaf(x, x, one), -y, zero};
+            acc_row<0b0111101>(acc, r, w0 * fx2, e0 * fx_inv);
         }
         {
-            const V r[7] = {zero, zj_inv, -yz, -vfma(y, y, one), xy, x, zero};
-            acc_row<0b0111110>(acc, r, w1 * vsplat(fy2, x), e1 * vsplat(fy_inv, x));
-        }
-#else
-        const V fx = vsplat(P.fx, x), fy = vsplat(P.fy, x);
-        {
-            const V r[7] = {fx * zj_inv, zero, -fx * xz, -fx * xy, fx * vfma(x, x, one), -fx * y, zero};
-            acc_row<0b0111101>(acc, r, w0, e0);
+            const float r[7] = {zero, zj_inv, -yz, -fmaf(y, y, one), xy, x, zero};
+            acc_row<0b0111110>(acc, r, w1 * fy2, e1 * fy_inv);
         }
         {
-            const V r[7] = {zero, fy * zj_inv, -fy * yz, -fy * vfma(y, y, one), fy * xy, fy * x, zero};
-            acc_row<0b0111110>(acc, r, w1, e1);
-        }
-#endif
-        {
-            const V r[7] = {zero, zero, zj_inv, y, -x, zero, one};
+            const float r[7] = {zero, zero, zj_inv, y, -x, zero, one};
             acc_row<0b1011100>(acc, r, w2, e2);
         }
     } else {
         // point_align_kernel, gn_kernels.cu:564-674
-        const V e0 = X0 - p.xi0, e1 = X1 - p.xi1, e2 = X2 - p.xi2;
-        const V swp = vsel(valid, vsplat(P.s0_inv, sq) * sq, zero);
-        const V wc = swp * swp;
-        const V w0 = huber(swp * e0) * wc;
-        const V w1 = huber(swp * e1) * wc;
-        const V w2 = huber(swp * e2) * wc;
-        const V one = vsplat(1.0f, X0);
+        const float e0 = X0 - p.xi0, e1 = X1 - p.xi1, e2 = X2 - p.xi2;
+        const float sw = P.s0_inv * sq;  // (the product first, then the select: not a product in one arm)
+        const float swp = valid ? sw : zero;
+        const float wc = swp * swp;
+        const float w0 = huber(swp * e0) * wc;
+        const float w1 = huber(swp * e1) * wc;
+        const float w2 = huber(swp * e2) * wc;
+        const float one = 1.0f;
         {
-            const V r[7] = {one, zero, zero, zero, X2, -X1, X0};
+            const float r[7] = {one, zero, zero, zero, X2, -X1, X0};
             acc_row<0b1110001>(acc, r, w0, e0);
         }
         {
-            const V r[7] = {zero, one, zero, -X2, zero, X0, X1};
+            const float r[7] = {zero, one, zero, -X2, zero, X0, X1};
             acc_row<0b1101010>(acc, r, w1, e1);
         }
         {
-            const V r[7] = {zero, zero, one, X1, -X0, zero, X2};
+            const float r[7] = {zero, zero, one, X1, -X0, zero, X2};
             acc_row<0b1011100>(acc, r, w2, e2);
         }
     }
 }
 
-template <int MODE, typename V>
-__device__ __forceinline__ void point_body(const PointsIn<V>& p, const RelXf& T, const AccParams& P,
-                                           V* __restrict__ acc) {
-    V X0, X1, X2;
+template <int MODE>
+__device__ __forceinline__ void point_body(const PointsIn& p, const RelXf& T, const AccParams& P,
+                                           float* __restrict__ acc) {
+    float X0, X1, X2;
     apply_rel(T, p.xj0, p.xj1, p.xj2, X0, X1, X2);
-    point_body_x<MODE, V>(p, X0, X1, X2, P, acc);
+    point_body_x<MODE>(p, X0, X1, X2, P, acc);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -422,12 +353,6 @@ __device__ __forceinline__ void block_partial(const float* accs, float* __restri
     }
 }
 
-
-// The ray-constrained calib stream's transform factored per pixel row (AccStage::compute; A/B
-// builds: -DM3S_RC_FACTOR=0 keeps s M x + t on the rebuilt point, bitwise the positional stream)
-#ifndef M3S_RC_FACTOR
-#define M3S_RC_FACTOR 1
-#endif
 
 // One pipeline stage of the packed accumulate: the records, Xj and the gathered matched points
 // of 4 consecutive points of one lane.
@@ -565,13 +490,13 @@ struct AccStage {
         const int* codes = cd;
         const int* sqb = sb;
         float xj[3 * NP];
-        // RC_FACTOR: the ray-constrained point is z (tu, tv, 1), so T_ij Xj = z (tu M_0 + B_v) + t
+        // RC: the ray-constrained point is z (tu, tv, 1), so T_ij Xj = z (tu M_0 + B_v) + t
         // with B_v = tv M_1 + M_2 shared by the lane's NP points (one pixel row): 6 FMAs per point
-        // and 3 per step instead of 2 multiplies + 9 FMAs per point (other roundings than the
-        // positional stream's s M x + t)
-        constexpr bool kFactor = RC && M == GN_CALIB && M3S_RC_FACTOR;
+        // and 3 per step instead of 2 multiplies + 9 FMAs per point on the rebuilt point
+        // x = z tu, y = z tv (other roundings than the positional stream's s M x + t)
+        static_assert(!RC || M == GN_CALIB, "the ray-constrained stream is calib's");
         float Xr[3 * NP];
-        if constexpr (kFactor) {
+        if constexpr (RC) {
             const float tv = xv[2 * NP];
             const float B0 = fmaf(T.m[1], tv, T.m[2]), B1 = fmaf(T.m[4], tv, T.m[5]), B2 = fmaf(T.m[7], tv, T.m[8]);
 #pragma unroll
@@ -581,20 +506,13 @@ struct AccStage {
                 Xr[3 * s + 1] = fmaf(z, fmaf(T.m[3], tu, B1), T.t[1]);
                 Xr[3 * s + 2] = fmaf(z, fmaf(T.m[6], tu, B2), T.t[2]);
             }
-        } else if constexpr (RC) {  // x = z * ((u - cx) / fx), y = z * ((v - cy) / fy): constrain_points_to_ray
-#pragma unroll
-            for (int s = 0; s < NP; s++) {
-                xj[3 * s] = xv[s] * xv[NP + s];
-                xj[3 * s + 1] = xv[s] * xv[2 * NP];
-                xj[3 * s + 2] = xv[s];
-            }
         } else {
 #pragma unroll
             for (int q = 0; q < 3 * NP; q++) xj[q] = xv[q];
         }
 #pragma unroll
         for (int s = 0; s < NP; s++) {
-            PointsIn<float> p;
+            PointsIn p;
             if constexpr (M == GN_CALIB) {
                 p.xi0 = p.xi1 = 0.0f;
                 if constexpr (PK)
@@ -608,20 +526,14 @@ struct AccStage {
             p.xi2 = g[s][2];
             p.valid = codes[s] >= 0;
             p.sq = __int_as_float(sqb[s]);
-            if constexpr (kFactor) {
-                point_body_x<M, float>(p, Xr[3 * s], Xr[3 * s + 1], Xr[3 * s + 2], P, acc);
+            if constexpr (RC) {
+                point_body_x<M>(p, Xr[3 * s], Xr[3 * s + 1], Xr[3 * s + 2], P, acc);
             } else {
                 p.xj0 = xj[3 * s];
                 p.xj1 = xj[3 * s + 1];
                 p.xj2 = xj[3 * s + 2];
-                point_body<M, float>(p, T, P, acc);
+                point_body<M>(p, T, P, acc);
             }
-#if M3S_ACC_SCHED_BARRIER == 1
-            __builtin_amdgcn_sched_barrier(0);  // one point's temporaries live at a time
-#elif M3S_ACC_SCHED_BARRIER == 2
-            // two points' temporaries at a time: their dependent residual chains interleave
-            if (s & 1) __builtin_amdgcn_sched_barrier(0);
-#endif
         }
     }
 };
@@ -630,14 +542,9 @@ struct AccStage {
 // of 112 VGPRs (points 61 / 75), 6 instead of 4 waves per SIMD; cfg4 accumulate 2.08 -> 1.96 ms.
 // Calib: 4, with the ray-constrained path (Xj read as its depth): 0.337 ms on cfg3 against 0.350
 // for the positional path at 2 and 0.358 for the ray-constrained one at 2 (profiles/r03_acc_ab.txt).
-// -DM3S_ACC_PPL=n forces n for every mode (A/B builds).
 template <int MODE>
 __host__ __device__ constexpr int acc_np() {
-#ifdef M3S_ACC_PPL
-    return M3S_ACC_PPL;
-#else
     return MODE == GN_CALIB ? 4 : 2;
-#endif
 }
 
 // Reads the reference's tensors directly every iteration (used when the call runs < 3
@@ -724,7 +631,7 @@ __global__ __launch_bounds__(kAccThreads) void gn_accum_kernel(
 #pragma unroll
         for (int q = 0; q < kNacc; q++) accs[q] = 0.0f;
         for (int k = k0 + tid; k < k1; k += kAccThreads) {
-            PointsIn<float> p;
+            PointsIn p;
             const bool vm = valid[k] != 0;
             const int ind = match_index(idx[k], vm, HW);
             const float q = Q[k];
@@ -738,7 +645,7 @@ __global__ __launch_bounds__(kAccThreads) void gn_accum_kernel(
             p.valid = vm && (q > P.Q_thresh) && (Ci_b[ind] > P.C_thresh) && (Cj_b[k] > P.C_thresh);
             p.sq = sqrt_cr(q);
             if constexpr (MODE == GN_CALIB) pixel_of(ind, P, p.ut, p.vt);
-            point_body<MODE, float>(p, T, P, accs);
+            point_body<MODE>(p, T, P, accs);
         }
     }
     block_partial(accs, partials + ((int64_t)e * P.nchunks + c) * kNaccPad);
@@ -947,8 +854,8 @@ __global__ __launch_bounds__(kAccThreads) void gn_pack_compact_kernel(
 // every point IS its pixel's ray times its depth, bit for bit, i.e. what solve_GN_calib's
 // constrain_points_to_ray (global_opt.py:172, geometry.py:37-42/107-123: z * ((u - cx) / fx))
 // produces.  If so (flag kFlagNotRay stays 0) the accumulate reads Xj as its 4-B depth and
-// applies T_ij to z (tu, tv, 1) factored per pixel row (M3S_RC_FACTOR; with it off, x and y are
-// rebuilt with the same two roundings and the result is bitwise the positional stream's).
+// applies T_ij to z (tu, tv, 1) factored per pixel row (AccStage::compute: other roundings than
+// the positional stream's).
 __global__ __launch_bounds__(256) void gn_depth_kernel(const float* __restrict__ Xs, int64_t total,
                                                        float* __restrict__ Zs, AccParams P,
                                                        int* __restrict__ flags, const float* __restrict__ K) {
@@ -1087,7 +994,6 @@ __device__ __forceinline__ void accum_steps(const float* __restrict__ Xj_b, cons
             records(r, na, nb);
             if constexpr (FIXC) cur.fix_columns(k0 + (int)r, S / P.width);
         }
-#if M3S_ACC_DIAG == 0
         // The step loop unrolled by two over two record sets used alternately: while one set is
         // computed on, the other receives the next step's records, so no set is copied into
         // another (a rotating pair cost 16 v_mov per step).  An odd step count leaves after the
@@ -1119,34 +1025,6 @@ __device__ __forceinline__ void accum_steps(const float* __restrict__ Xj_b, cons
             step(ma, mb, r);
             r += S;
         }
-#else
-        const unsigned r0 = r;
-        for (; r < n; r += S) {
-#if M3S_ACC_DIAG == 1
-            // diagnostics: compute only (the first step's data, re-used: no memory after it)
-            if (r == r0) {
-                cur.set(na, nb);
-                cur.template load<MODE, FIXC>(Xj_c, Xi_b, Zi_b, r, k0 + (int)r);
-            }
-            cur.template compute<MODE>(T, P, acc);
-            __builtin_amdgcn_sched_barrier(0);
-#else
-            // diagnostics: memory only -- the first step computed (so the system stays solvable and
-            // the iterations keep running), then every step's loads with each value merely consumed
-            cur.set(na, nb);
-            if (r + S < n) records(r + S, na, nb);
-            cur.template load<MODE, FIXC>(Xj_c, Xi_b, Zi_b, r, k0 + (int)r);
-            if (r == r0) {
-                cur.template compute<MODE>(T, P, acc);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 3 * NP; q++) asm volatile("" ::"v"(cur.xv[q]));
-#pragma unroll
-                for (int q = 0; q < NP; q++) asm volatile("" ::"v"(cur.g[q][2]), "v"(cur.g[q][0]), "v"(cur.cd[q]), "v"(cur.sb[q]));
-            }
-#endif
-        }
-#endif
     };
     if constexpr (RC) {
         if (S % P.width == 0)  // (workgroup-uniform; cfg3: 1024 points per step, W = 512)
@@ -1160,18 +1038,6 @@ __device__ __forceinline__ void accum_steps(const float* __restrict__ Xj_b, cons
 
 // Per-iteration accumulate over the packed stream: 8 B {code, sqrt q} + Xj 12 B + the gather
 // of the matched point (calib: its depth from Zs; rays/points: Xi) per point-edge.
-
-#ifndef M3S_ACC_WAVES
-#define M3S_ACC_WAVES 1
-#endif
-// the rays iteration kernel's occupancy floor (A/B builds; 1 = the compiler's choice)
-#ifndef M3S_ACC_WAVES_RAYS
-#define M3S_ACC_WAVES_RAYS M3S_ACC_WAVES
-#endif
-template <int MODE, bool FIRST>
-constexpr int acc_waves() {
-    return (MODE == GN_RAYS && !FIRST) ? M3S_ACC_WAVES_RAYS : M3S_ACC_WAVES;
-}
 // FIRST (calib, the positional stream): the first iteration of a call, building the packed
 // records from the reference's inputs on the way (RawSrc; no separate gn_pack_kernel pass).
 struct FirstSrc {
@@ -1182,8 +1048,7 @@ struct FirstSrc {
 };
 
 template <int MODE, bool COMPACT, bool RCOK = false, bool FIRST = false>
-__global__ __launch_bounds__(kAccThreads) __attribute__((amdgpu_waves_per_eu(acc_waves<MODE, FIRST>())))
-void gn_accum_packed_kernel(
+__global__ __launch_bounds__(kAccThreads) void gn_accum_packed_kernel(
     const float* __restrict__ Twc, const float* __restrict__ Xs, const float* __restrict__ Zs,
     const int* __restrict__ ii_loc, const int* __restrict__ jj_loc, const int4* __restrict__ pack,
     AccParams P, const int4* __restrict__ sched, float* __restrict__ partials,
@@ -1215,23 +1080,25 @@ void gn_accum_packed_kernel(
         const int64_t cb = ((int64_t)e * P.nchunks + c) * P.chunk;
         accum_steps<MODE, false, acc_np<MODE>()>(px + cb * 3, Xi_b, Zi_b, pack + cb / 2, 0, pcnt[(int64_t)e * P.nchunks + c], T, P,
                                  Zs, acc);
-    } else if constexpr (FIRST) {
-        RawSrc raw;
-        fs.es.at(e, HW, raw.idx, raw.valid, raw.Q);
-        raw.Ci_b = fs.Cs + (int64_t)ix * HW;
-        raw.Cj_b = fs.Cs + (int64_t)jx * HW;
-        raw.pk_w = fs.pack_w + ebase / 2;
-        raw.ci_all = fs.cok != nullptr && fs.cok[ix] != 0;
-        raw.cj_all = fs.cok != nullptr && fs.cok[jx] != 0;
-        if (RCOK && flags[kFlagNotRay] == 0 && (P.width & 3) == 0)
-            accum_steps<MODE, true, 4, true>(Zs + (int64_t)jx * HW, Xi_b, Zi_b, pk_b, k0, k1, T, P, Zs, acc, raw);
-        else
-            accum_steps<MODE, false, acc_np<MODE>(), true>(Xj_b, Xi_b, Zi_b, pk_b, k0, k1, T, P, Zs, acc, raw);
-    } else if (RCOK && MODE == GN_CALIB && flags[kFlagNotRay] == 0 && (P.width & 3) == 0)
+    } else {
+        RawSrc raw{};
+        if constexpr (FIRST) {
+            fs.es.at(e, HW, raw.idx, raw.valid, raw.Q);
+            raw.Ci_b = fs.Cs + (int64_t)ix * HW;
+            raw.Cj_b = fs.Cs + (int64_t)jx * HW;
+            raw.pk_w = fs.pack_w + ebase / 2;
+            raw.ci_all = fs.cok != nullptr && fs.cok[ix] != 0;
+            raw.cj_all = fs.cok != nullptr && fs.cok[jx] != 0;
+        }
+        constexpr int NP = acc_np<MODE>();
         // calib with ray-constrained keyframe points (gn_depth_kernel's check): Xj from its depth
-        accum_steps<MODE, true, acc_np<MODE>()>(Zs + (int64_t)jx * HW, Xi_b, Zi_b, pk_b, k0, k1, T, P, Zs, acc);
-    else
-        accum_steps<MODE, false, acc_np<MODE>()>(Xj_b, Xi_b, Zi_b, pk_b, k0, k1, T, P, Zs, acc);
+        bool ray = false;
+        if constexpr (RCOK && MODE == GN_CALIB) {
+            ray = flags[kFlagNotRay] == 0 && (P.width & 3) == 0;
+            if (ray) accum_steps<MODE, true, NP, FIRST>(Zs + (int64_t)jx * HW, Xi_b, Zi_b, pk_b, k0, k1, T, P, Zs, acc, raw);
+        }
+        if (!ray) accum_steps<MODE, false, NP, FIRST>(Xj_b, Xi_b, Zi_b, pk_b, k0, k1, T, P, Zs, acc, raw);
+    }
     block_partial(acc, partials + ((int64_t)e * P.nchunks + c) * kNaccPad, ecnt != nullptr);
     if (ecnt != nullptr) {
         // fused edge reduce: the edge's last workgroup to finish sums its chunk partials (in

@@ -48,19 +48,6 @@
 #include "gn_kernels.h"
 #include "sim3.h"
 
-// 1: the tail's pose step factors L_KK in every thread and fuses the panel-row solve into it
-// (no L_KK^-1 round trip through LDS, one barrier less per pose); 0: wave 0 factors and inverts,
-// a barrier, then a matvec per panel row
-#ifndef M3S_TAIL_FUSED_A
-#define M3S_TAIL_FUSED_A 1
-#endif
-// Diagnostic builds only (timing; the results are wrong): bit 1 = no L row stores to global in
-// the tail's phase A, bit 2 = no rank-7 MFMA update, bit 4 = no next-panel extraction, bit 8 =
-// no 7x7 factor / forward substitutions in phase A
-#ifndef M3S_TAIL_DIAG
-#define M3S_TAIL_DIAG 0
-#endif
-
 namespace m3s {
 
 namespace {
@@ -149,21 +136,6 @@ __device__ __forceinline__ void bwd7(const double (&L)[28], const double (&inv)[
         z[c] *= inv[c];
 #pragma unroll
         for (int m = 0; m < c; m++) z[m] = fma(-L[pk(c, m)], z[c], z[m]);
-    }
-}
-
-// Li = L^-1 (packed lower) from L and inv = 1/diag
-[[maybe_unused]] __device__ __forceinline__ void inv7(const double (&L)[28], const double (&inv)[7], double (&Li)[28]) {
-#pragma unroll
-    for (int j = 0; j < 7; j++) {
-        Li[pk(j, j)] = inv[j];
-#pragma unroll
-        for (int i = j + 1; i < 7; i++) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = j; k < i; k++) s = fma(L[pk(i, k)], Li[pk(k, j)], s);
-            Li[pk(i, j)] = -s * inv[i];
-        }
     }
 }
 
@@ -270,13 +242,10 @@ __device__ __forceinline__ void tail_solve(const SolveArgs& a, const int* __rest
     }
     lds_barrier();
     tick(6);
-#if M3S_TAIL_FUSED_A
     double yprev[7];  // y of the previous pose, written to sZ by one thread a phase later
-#endif
     for (int K = 0; K < nt; K++) {
         const int c0 = 7 * K;
         const int nrows = n - c0 - 7;  // panel rows below the diagonal block
-#if M3S_TAIL_FUSED_A
         // A. every thread factors L_KK in registers (redundantly: no barrier, no L_KK^-1 round
         //    trip through LDS) and runs two forward substitutions: y_K = L_KK^-1 z_K and one
         //    input of its role -- panel row i = c0+7+tid (its row of L, RHS update), or, for the
@@ -301,25 +270,16 @@ __device__ __forceinline__ void tail_solve(const SolveArgs& a, const int* __rest
 #pragma unroll
             for (int c = 0; c < 7; c++) in[c] = prow ? sPn[i * kSS + so + c] : (c == m ? 1.0 : 0.0);
             const double zr0 = prow ? sZ[i] : 0.0;
-#if M3S_TAIL_DIAG & 8
-#pragma unroll
-            for (int c = 0; c < 7; c++) {
-                yK[c] = z[c] + L[pk(c, c)];
-                out[c] = in[c] + L[pk(6, c)];
-                inv[c] = 1.0;
-            }
-#else
             chol7(L, inv, bad);
             fwd7(L, inv, z, yK);
             fwd7(L, inv, in, out);
-#endif
             if (prow) {
                 double* Lg = a.Lg + (int64_t)i * n + c0;
                 double zr = zr0;
 #pragma unroll
                 for (int c = 0; c < 7; c++) {
                     sPop[i * kPS + c] = out[c];
-                    if (!(M3S_TAIL_DIAG & 1)) Lg[c] = out[c];
+                    Lg[c] = out[c];
                     zr = fma(-out[c], yK[c], zr);
                 }
                 sZ[i] = zr;
@@ -335,74 +295,10 @@ __device__ __forceinline__ void tail_solve(const SolveArgs& a, const int* __rest
             }
         }
         if (K >= 3 && K < 5) tick(7);
-#else
-        // A1. wave 0: L_KK (in-lane serial, every lane), L_KK^-1 and y_K = L_KK^-1 z_K
-        if (W == 0) {
-            double L[28], inv[7], z[7], y[7], Li[28];
-#pragma unroll
-            for (int i = 0; i < 7; i++) {
-#pragma unroll
-                for (int j = 0; j <= i; j++) L[pk(i, j)] = sPn[(c0 + i) * kSS + (c0 & 15) + j];
-                z[i] = sZ[c0 + i];
-            }
-            chol7(L, inv, bad);
-            inv7(L, inv, Li);
-#pragma unroll
-            for (int c = 0; c < 7; c++) {
-                double s2 = 0.0;
-#pragma unroll
-                for (int m = 0; m <= c; m++) s2 = fma(Li[pk(c, m)], z[m], s2);
-                y[c] = s2;
-            }
-            // every lane holds the same values: lane 0 stores them (no per-lane select chains
-            // on the critical path)
-            if (lane == 0) {
-#pragma unroll
-                for (int k = 0; k < 28; k++) sL[K * kLRec + k] = Li[k];
-#pragma unroll
-                for (int c = 0; c < 7; c++) sZ[c0 + c] = y[c];
-            }
-        }
-        if (K >= 3 && K < 5) tick(7);
-        lds_barrier();
-        // A2. panel rows of L: P_i = L_KK^-1 a_i (matvec), RHS update
-        {
-            const double* Li = sL + K * kLRec;
-            const int i = c0 + 7 + tid;
-            if (tid < nrows) {
-                double in[7], out[7], y[7];
-#pragma unroll
-                for (int c = 0; c < 7; c++) {
-                    in[c] = sPn[i * kSS + (c0 & 15) + c];
-                    y[c] = sZ[c0 + c];
-                }
-                double zr = sZ[i];
-                double* Lg = a.Lg + (int64_t)i * n + c0;
-#pragma unroll
-                for (int c = 0; c < 7; c++) {
-                    double s2 = 0.0;
-#pragma unroll
-                    for (int m = 0; m <= c; m++) s2 = fma(Li[pk(c, m)], in[m], s2);
-                    out[c] = s2;
-                    sPop[i * kPS + c] = s2;
-                    Lg[c] = s2;
-                    zr = fma(-s2, y[c], zr);
-                }
-                sZ[i] = zr;
-            }
-            if (tid >= kThreads - 7) {  // the pose's own rows leave the MFMA operand
-                const int rr = c0 + (tid - (kThreads - 7));
-#pragma unroll
-                for (int c = 0; c < 8; c++) sPop[rr * kPS + c] = 0.0;
-            }
-        }
-#endif
         if (K >= 3 && K < 5) tick(8);
         lds_barrier();
-#if M3S_TAIL_FUSED_A
 #pragma unroll
         for (int c = 0; c < 7; c++) yprev[c] = yK[c];  // stored at the next phase A (or after the loop)
-#endif
         // B. -C_IJ += P_I P_J^T for the live tiles (J >= Jmin), operands from registers.  The
         //    slots are sorted by J, so the live ones are a suffix [kf, NS): a fall-through
         //    switch enters the unrolled MFMA sequence at kf with no per-slot tests.  Then the
@@ -422,7 +318,7 @@ __device__ __forceinline__ void tail_solve(const SolveArgs& a, const int* __rest
             for (int k = 0; k < NS; k++) kf += SM.J[k] < Jmin;
 #define M3S_MF(k)                                                                                 \
     case k:                                                                                       \
-        if constexpr (k < NS && !(M3S_TAIL_DIAG & 2)) {                                           \
+        if constexpr (k < NS) {                                                                   \
             acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(P0[SM.I[k]], P0[SM.J[k]], acc[k], 0, 0, 0); \
             acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(P1[SM.I[k]], P1[SM.J[k]], acc[k], 0, 0, 0); \
         }                                                                                         \
@@ -437,7 +333,7 @@ __device__ __forceinline__ void tail_solve(const SolveArgs& a, const int* __rest
             }
 #undef M3S_MF
             static_assert(NS <= 32, "tail slot map exceeds the unrolled MFMA switch");
-            if (K + 1 < nt && !(M3S_TAIL_DIAG & 4)) {
+            if (K + 1 < nt) {
                 // the next pose's strip: its tile columns J0 and J1 (= J0 or J0 + 1), whole tiles
                 const int c1 = c0 + 7;
                 const int J0 = c1 >> 4, J1 = (c1 + 6) >> 4;
@@ -461,12 +357,10 @@ __device__ __forceinline__ void tail_solve(const SolveArgs& a, const int* __rest
         else tick(15);  // a whole pose step
     }
     tick(2);
-#if M3S_TAIL_FUSED_A
     if (nt > 0 && tid == kThreads - 8) {
 #pragma unroll
         for (int c = 0; c < 7; c++) sZ[7 * (nt - 1) + c] = yprev[c];
     }
-#endif
 
     __syncthreads();  // the L rows (global, written by every wave) are read below
     // back-substitution L^T x = y over the tail, right-looking: x_K = L_KK^-T z_K, then every

@@ -419,7 +419,7 @@ def _ray_path_taken(backend, g, iters, monkeypatch):
 def test_ray_constrained_calib_path(backend, oracle, monkeypatch, iters):
     """solve_GN_calib hands the op ray-constrained points (global_opt.py:172); the packed calib
     accumulate then reads Xj as its depth (gn_depth_kernel checks every point bit for bit) and
-    applies T_ij to z (tu, tv, 1) factored per pixel row (M3S_RC_FACTOR), other roundings than
+    applies T_ij to z (tu, tv, 1) factored per pixel row (AccStage::compute), other roundings than
     the positional stream's s M x + t: both within 1e-5 of the oracle and of each other to float
     rounding.  The path must not be taken for unconstrained points (then the result is bitwise
     the positional stream's)."""

@@ -1,7 +1,8 @@
-// Diagnostic: the chain workgroup's 64x64 tile LL^T + inverse (chol_df.hip potrf_inverse) alone,
-// one workgroup per tile, with cycle stamps inside every panel step (M3S_DF_STAMPS): when wave 0
-// finished its look-ahead trailing update, its panel factor, when wave 3 finished its share, and
-// when the step's barrier released.  Checks L L^T = A and Li L = I against the input.
+// Diagnostic: the chain workgroup's 64x64 tile LL^T + inverse (chol_df.hip potrf_bc) alone, one
+// workgroup per tile, with cycle stamps per wave (M3S_DF_STAMPS): when each of its batches was
+// published, when its X_ww was written and when it finished; with -DM3S_DF_BSTAMPS=1 also per
+// batch the critical wait and apply, and the inverse's written-wait.  Checks L L^T = A and
+// Li L = I against the input and prints a bit digest of L and Li.  Plus one-wave latency probes.
 #define M3S_DF_STAMPS 1
 #include "../mast3r-slam_amd/csrc/chol_df.hip"
 
@@ -22,37 +23,14 @@
 
 namespace m3s {
 namespace {
-__global__ __launch_bounds__(NT) void k_potrf(const double* __restrict__ A0, double* __restrict__ Lout,
-                                              double* __restrict__ Liout, long long* __restrict__ pt,
-                                              int* __restrict__ flags) {
-    __shared__ __attribute__((aligned(16))) double X[T * LD];
-    __shared__ __attribute__((aligned(16))) double Y[T * LD];
-    __shared__ __attribute__((aligned(16))) double Z[T * LD];
-    __shared__ double Dinv[T];
-    const int tid = threadIdx.x;
-    const double* A = A0 + (size_t)blockIdx.x * T * T;
-    for (int id = tid; id < T * T; id += NT) Z[(id >> 6) * LD + (id & 63)] = A[id];
-    for (int id = tid; id < T * LD; id += NT) Y[id] = 0.0;
-    __syncthreads();
-    long long* p = pt + (size_t)blockIdx.x * 64;
-    const long long t0 = (long long)__builtin_amdgcn_s_memtime();
-    if (tid == 0) p[60] = t0;
-    potrf_inverse(Z, Y, X, Dinv, flags, p, nullptr, 0);
-    const long long t1 = (long long)__builtin_amdgcn_s_memtime();
-    if (tid == 0) p[61] = t1;
-    for (int id = tid; id < T * T; id += NT) {
-        Lout[(size_t)blockIdx.x * T * T + id] = Z[(id >> 6) * LD + (id & 63)];
-        Liout[(size_t)blockIdx.x * T * T + id] = Y[(id >> 6) * LD + (id & 63)];
-    }
-}
-__global__ __launch_bounds__(NT) void k_potrf_cc(const double* __restrict__ A0, double* __restrict__ Lout,
+__global__ __launch_bounds__(NT) void k_potrf_bc(const double* __restrict__ A0, double* __restrict__ Lout,
                                                  double* __restrict__ Liout, long long* __restrict__ pt,
                                                  int* __restrict__ flags) {
     __shared__ __attribute__((aligned(16))) double X[T * LD];
     __shared__ __attribute__((aligned(16))) double Y[T * LD];
     __shared__ __attribute__((aligned(16))) double Z[T * LD];
     __shared__ double Dinv[T];
-    __shared__ double Scr[kCcScr];
+    __shared__ double Scr[kBcScr];
     __shared__ int Sync[kDfSync];
     const int tid = threadIdx.x;
     const double* A = A0 + (size_t)blockIdx.x * T * T;
@@ -63,7 +41,7 @@ __global__ __launch_bounds__(NT) void k_potrf_cc(const double* __restrict__ A0, 
     long long* p = pt + (size_t)blockIdx.x * 64;
     const long long t0 = (long long)__builtin_amdgcn_s_memtime();
     const long long r0 = (long long)__builtin_amdgcn_s_memrealtime();
-    potrf_cc(Z, Y, X, Scr, Sync, Dinv, flags, p);
+    potrf_bc(Z, Y, X, Scr, Sync, Dinv, flags, p);
     const long long t1 = (long long)__builtin_amdgcn_s_memtime();
     const long long r1 = (long long)__builtin_amdgcn_s_memrealtime();
     if (tid == 0) {
@@ -151,30 +129,7 @@ int main(int argc, char** argv) {
     CK(hipMemset(dfl, 0, 64 * 4));
     CK(hipMemset(dpt, 0, (size_t)ntile * 64 * 8));
     CK(hipMemcpy(dA, A.data(), A.size() * 8, hipMemcpyHostToDevice));
-    for (int rep = 0; rep < 3; rep++) {
-        hipLaunchKernelGGL(k_potrf, dim3(ntile), dim3(NT), 0, 0, dA, dL, dLi, dpt, dfl);
-        CK(hipDeviceSynchronize());
-    }
     std::vector<double> L(A.size()), Li(A.size());
-    std::vector<long long> pt((size_t)ntile * 64);
-    CK(hipMemcpy(L.data(), dL, A.size() * 8, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(Li.data(), dLi, A.size() * 8, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(pt.data(), dpt, pt.size() * 8, hipMemcpyDeviceToHost));
-    double eLL = 0, eLi = 0;
-    for (int t = 0; t < ntile; t++) {
-        const double* a = &A[(size_t)t * 4096];
-        const double* l = &L[(size_t)t * 4096];
-        const double* li = &Li[(size_t)t * 4096];
-        for (int r = 0; r < 64; r++)
-            for (int c = 0; c <= r; c++) {
-                double s = 0, u = 0;
-                for (int k = 0; k <= c; k++) s += l[r * 64 + k] * l[c * 64 + k];
-                for (int k = c; k <= r; k++) u += li[r * 64 + k] * l[k * 64 + c];
-                eLL = std::max(eLL, std::fabs(s - a[r * 64 + c]));
-                eLi = std::max(eLi, std::fabs(u - (r == c ? 1.0 : 0.0)));
-            }
-    }
-    printf("max |L L^T - A| %.3e, max |Li L - I| %.3e\n", eLL, eLi);
     auto check = [&](const char* name) {
         double e1 = 0, e2 = 0;
         for (int t = 0; t < ntile; t++) {
@@ -204,33 +159,29 @@ int main(int argc, char** argv) {
     };
     CK(hipMemset(dpt, 0, (size_t)ntile * 64 * 8));
     for (int rep = 0; rep < 3; rep++) {
-        hipLaunchKernelGGL(k_potrf_cc, dim3(ntile), dim3(NT), 0, 0, dA, dL, dLi, dpt, dfl);
+        hipLaunchKernelGGL(k_potrf_bc, dim3(ntile), dim3(NT), 0, 0, dA, dL, dLi, dpt, dfl);
         CK(hipDeviceSynchronize());
     }
     std::vector<long long> pc((size_t)ntile * 64);
     CK(hipMemcpy(L.data(), dL, A.size() * 8, hipMemcpyDeviceToHost));
     CK(hipMemcpy(Li.data(), dLi, A.size() * 8, hipMemcpyDeviceToHost));
     CK(hipMemcpy(pc.data(), dpt, pc.size() * 8, hipMemcpyDeviceToHost));
-    check("potrf_cc");
+    check("potrf_bc");
     {
         long long tc = 0, rc = 0;
         for (int t = 0; t < ntile; t++) {
             tc += pc[(size_t)t * 64 + 61] - pc[(size_t)t * 64 + 60];
             rc += pc[(size_t)t * 64 + 62];
         }
-        printf("potrf_cc: mean %.0f cycles, %.2f us (s_memrealtime)\n", (double)tc / ntile, rc * 0.01 / ntile);
-        printf("potrf_cc tile 0, cycles from start: wave: applied / factored / diag-inv start / X_ww / X_Vw...\n");
+        printf("potrf_bc: mean %.0f cycles, %.2f us (s_memrealtime)\n", (double)tc / ntile, rc * 0.01 / ntile);
+        printf("potrf_bc tile 0, cycles from start: wave: batches 0-3 published / X_ww / end\n");
         for (int w = 0; w < 4; w++) {
             printf("  wave %d:", w);
-#if M3S_DF_BC
             for (int k = 1; k <= 6; k++) printf(" %7lld", pc[8 * w + k] - pc[60]);  // batches lb 0-3 / X_ww / end
-#else
-            for (int k = 1; k < 4 + 3 - w; k++) printf(" %7lld", pc[8 * w + k] - pc[60]);
-#endif
             printf("\n");
         }
         printf("  end: %lld\n", pc[61] - pc[60]);
-#if M3S_DF_BC && M3S_DF_BSTAMPS
+#if M3S_DF_BSTAMPS
         printf("per batch (cycles): previous publish -> wait done -> critical apply done -> publish\n");
         for (int nb = 1; nb < 16; nb++) {
             auto pub = [&](int b) { return pc[8 * (b & 3) + 1 + (b >> 2)]; };
@@ -242,19 +193,5 @@ int main(int argc, char** argv) {
             printf("  wave %d: %6lld %6lld %6lld\n", w, pc[52 + w] - pc[60], pc[8 * w + 5] - pc[60], pc[8 * w + 6] - pc[60]);
 #endif
     }
-    // cycles (s_memtime) for tile 0: per panel step, relative to the previous step's barrier
-    const long long* p = &pt[0];
-    long long prev = p[60];
-    printf("total %lld cycles (%.2f us at 2.4 GHz)\n", p[61] - p[60], (p[61] - p[60]) / 2400.0);
-    printf("step : w0 trail  w0 factor  w3 done  barrier (cycles since the previous barrier)\n");
-    for (int s = 0; s < 7; s++) {
-        printf("  %d  : %7lld %9lld %8lld %8lld\n", s, p[20 + 4 * s] - prev, p[21 + 4 * s] - prev,
-               p[22 + 4 * s] - prev, p[23 + 4 * s] - prev);
-        prev = p[23 + 4 * s];
-    }
-    printf("after the steps: inverse stages %lld cycles\n", p[61] - prev);
-    long long tot = 0;
-    for (int t = 0; t < ntile; t++) tot += pt[(size_t)t * 64 + 61] - pt[(size_t)t * 64 + 60];
-    printf("mean over %d tiles: %.0f cycles\n", ntile, (double)tot / ntile);
     return 0;
 }
