@@ -381,7 +381,11 @@ int m3s_track_last_result(int32_t* info4, double* cost);
  * pass over B keyframe pairs:
  *   Qj = sqrt(Qii[b, idx_i2j] * Qji), Qi = sqrt(Qjj[b, idx_j2i] * Qij)     [B,HW] f32 out
  *   counts[b] = (#(valid_match_j & Qj > Q_conf), #(valid_match_i & Qi > Q_conf))  [B,2] i32 out
- *   idx_* [B,HW] i64, valid_match_* [B,HW] u8, Q* [B,HW] f32.  Bit-exact (same f32 ops).
+ *   idx_* [B,HW] i64, valid_match_* [B,HW] u8, Q* [B,HW] f32.  Bit-exact (same f32 ops: the
+ *   product, a correctly rounded sqrt, an f32 compare; a NaN Q is not counted).
+ * An index outside [0, HW-1] is clamped to 0 or HW-1 of the pair's own row (the reference would
+ * read out of range): nothing outside Qii[b] / Qjj[b] is read.  counts is zeroed by every call;
+ * B == 0 returns at once, HW == 0 zeroes counts and needs no other pointer.
  */
 int m3s_edge_confidence(const int64_t* idx_i2j, const int64_t* idx_j2i,
                         const uint8_t* valid_match_j, const uint8_t* valid_match_i,
@@ -399,7 +403,13 @@ enum { M3S_FILTER_WEIGHTED_POINTMAP = 0, M3S_FILTER_INDEP_CONF = 1, M3S_FILTER_R
  * the transform of the new observation the tracker applies first (tracker.py:98-99).
  *   T      [8] f32 Sim3 data applied to X_new (lietorch act), or NULL for none
  *   X_new  [HW,3], C_new [HW] f32; X [HW,3], C [HW] f32 updated in place
- * Bit-exact against the torch expressions on the same (transformed) inputs.
+ * The update is bit-exact against the torch expressions on the same (transformed) inputs: every
+ * product, sum and quotient rounded to f32, the divide correctly rounded, subnormals kept;
+ * indep_conf replaces where C_new > C strictly (a NaN replaces nothing).  The transform is
+ * act_so3 (the rotation, at the default contraction convention M3S_CONTRACT_NVCC: its sums of
+ * products fused) followed by an unfused s * r + t; it is within 8 * 2^-24 * (5 |s| |p| + max|t|)
+ * of the exact s R(q) p + t at every point (tests/keyframe_model.py act_bound), and a mode with T
+ * is bit for bit that mode on the output of "recent" with T.  HW == 0 returns without a launch.
  */
 int m3s_pointmap_update(int mode, const float* T, const float* X_new, const float* C_new,
                         float* X, float* C, int64_t HW, void* stream);
@@ -413,7 +423,7 @@ int m3s_pointmap_update(int mode, const float* T, const float* X_new, const floa
  *   kept    C[k,n] / n_obs[k] > thresh       (f32 divide and compare; NaN is not kept)
  *   point   p = X[k,n]; with K, p = z ((u - cx) / fx, (v - cy) / fy, 1), z = X[k,n,2],
  *           u = n % width, v = n / width  (geometry.py:37-42, f32 subtract / divide / multiply);
- *           pW = s R(q) p + t of T_WC[k]  (the act of m3s_pointmap_update, uncontracted)
+ *           pW = s R(q) p + t of T_WC[k]  (the act of m3s_pointmap_update, bit for bit)
  *   record  <f4 x, f4 y, f4 z, u1 r, u1 g, u1 b>: 15 bytes, packed, little-endian
  * count: counts [N] i64 = kept points per keyframe, total [1] i64 = their sum (both device); leaves
  *   the tile offsets in ws.  emit: follows a count with the same args and ws on the same stream;

@@ -7,7 +7,9 @@
 // (torch: two gathers, two products, two sqrts, two compares, two ands, two reductions over
 // [B,HW,1] tensors) in one pass: per pixel and direction 8 B index + 1 B mask + 4 B own Q +
 // 4 B gathered Q read, 4 B written.  Q is computed with the same two f32 operations (product,
-// correctly rounded sqrt) -> bit-exact; the counts are integers (exact in any order).
+// correctly rounded sqrt) -> bit-exact; the counts are integers (exact in any order).  A NaN Q is
+// not counted.  An index outside [0, HW-1] is clamped into the pair's own row (the reference would
+// fault), so nothing outside Qii[b] / Qjj[b] is read.  counts is zeroed by every call.
 #include <hip/hip_runtime.h>
 
 #include "../../include/m3s_backend.h"
@@ -66,12 +68,13 @@ extern "C" int m3s_edge_confidence(const int64_t* idx_i2j, const int64_t* idx_j2
                                    float* Qj, float* Qi, int* counts, void* stream) {
     M3S_REQUIRE(B >= 0 && HW >= 0, "edge_confidence: negative sizes");
     if (B == 0) return M3S_OK;
-    M3S_REQUIRE(idx_i2j && idx_j2i && valid_match_j && valid_match_i && Qii && Qjj && Qji && Qij &&
-                    Qj && Qi && counts,
-                "edge_confidence: null pointer");
+    M3S_REQUIRE(counts, "edge_confidence: null pointer");
     hipStream_t st = (hipStream_t)stream;
     M3S_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int) * 2 * (size_t)B, st));
-    if (HW == 0) return M3S_OK;
+    if (HW == 0) return M3S_OK;  // B pairs of no pixels: their counts are 0, the rest is empty
+    M3S_REQUIRE(idx_i2j && idx_j2i && valid_match_j && valid_match_i && Qii && Qjj && Qji && Qij &&
+                    Qj && Qi,
+                "edge_confidence: null pointer");
     // ~8 workgroups per CU over the whole batch, at least one chunk per pair
     int64_t chunks = (2048 + B - 1) / B;
     const int64_t max_chunks = (HW + m3s::kEdgeThreads - 1) / m3s::kEdgeThreads;

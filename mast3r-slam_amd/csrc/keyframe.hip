@@ -8,8 +8,15 @@
 //   recent             X <- Xn, C <- Cn                                 (frame.py:58-61)
 // torch runs weighted_pointmap as 5 elementwise kernels over [HW,3] / [HW,1] tensors (plus
 // the act); here one pass reads X, C, Xn, Cn and writes X, C: 32 B per point.  Each f32
-// operation is the same as torch's and nothing is contracted (-ffp-contract=off in the
-// Makefile), so the update is bit-exact against the torch expression on the same inputs.
+// operation of the update is the same as torch's and none of them is contracted
+// (-ffp-contract=off in the Makefile), so the update is bit-exact against the torch expression on
+// the same (transformed) inputs, 0/0, NaN, Inf and subnormals included.
+// The transform is the rotation act_so3 at the library's default contraction convention (sim3.h,
+// contract.h: its sums of products are fused as the reference's GN kernels fuse them) followed by
+// an unfused s * r + t: f32 arithmetic of its own, not any torch expression's bits.  The tests
+// hold it to the float64 transform within 8 * 2^-24 * (5 |s| |p| + max|t|) per point
+// (tests/keyframe_model.py act_bound; worst seen 0.84 of the unit 2^-24 * (...)), and every mode
+// with T equals, bit for bit, the same mode given the "recent"-with-T output as the observation.
 #include <hip/hip_runtime.h>
 
 #include "../../include/m3s_backend.h"

@@ -93,7 +93,12 @@ class Frame:
         self.N_updates += 1
 
     def get_average_conf(self):  # frame.py:107-108
-        return self.C / self.N if self.C is not None else None
+        if self.C is None:
+            return None
+        # a device tensor as the divisor: by a Python number torch multiplies with the rounded
+        # reciprocal on the device, which for N = 3, 5, ... is not the correctly rounded quotient
+        # that the reference gives on the host, KeyframeStore keeps (C / n_obs) and recon.hip divides
+        return self.C / torch.full((), self.N, dtype=self.C.dtype, device=self.C.device)
 
 
 def _identity():
